@@ -9,8 +9,14 @@ GPU (torchrun), each checksumming its own batch: the path shards with no
 exchange, so there is no data-path collective and scaling is
 weak. value = Σ bytes over all ranks ÷ max over ranks of the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2-18] [--no-pseudo]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2-18] [--no-pseudo] [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
+
+A plain run does what the headline figure needs and no more: set up the batch, settle, W warm-up steps, the K
+timed steps, the line. `--full` adds the CPU baseline leg (`cpu_baseline`, `--cpu-seconds` of host time after
+the timed region); without it the line's `cpu_baseline` is null. `--dump-outputs DIR` writes what the last timed
+step computed as DIR/<name>.npy (float32; see dump_outputs) so that two builds can be compared output for output:
+with the same arguments the inputs are the same bytes from run to run.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment launches the N rank
 processes itself (a torch.distributed.run child, rendezvous at 127.0.0.1) before
@@ -48,7 +54,8 @@ Printed by rank 0: one JSON line with the contract fields plus
                  the K timed steps, per launch) vs 8 TB/s HBM;
                  traffic = PMC-measured HBM bytes per launch from the committed
                  rocprofv3 summary (profiles/), or null;
-  cpu_baseline — the Go-faithful CPU restatement (oracle) timed on a bounded
+  cpu_baseline — with --full (null otherwise):
+                 the Go-faithful CPU restatement (oracle) timed on a bounded
                  sample of the same workload (rank 0, N=1 only) on every host
                  core this process may use (`cores`), with the 1-thread rate
                  beside it;
@@ -60,7 +67,8 @@ Printed by rank 0: one JSON line with the contract fields plus
 The product library is brought up to date (`make -C network-stack_amd`, a no-op
 when nothing changed, under a file lock) before it is loaded — by the launching
 process, or by each rank an outside launcher started — so a stale pushed binary
-never runs.
+never runs. A user who cannot write to the tree (someone else built it) builds
+nothing: the library is loaded as it stands, and the line's `library_build` says so.
 """
 from __future__ import annotations
 
@@ -187,7 +195,13 @@ def parse_args(argv=None):
                          "IPv4 frames of 40-400 B")
     ap.add_argument("--no-pseudo", action="store_true",
                     help="configs 2 and 5: checksum the segments without their pseudo-header partials")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline sample budget (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline leg (cpu_baseline, "
+                         "with its parity check against the GPU's results), --cpu-seconds of host time")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0,
+                    help="--full: CPU baseline sample budget (0 = skip)")
     ap.add_argument("--settle-s", type=float, default=0.5, help="device clock settle time before warmup (setup)")
     ap.add_argument("--tune", action="append", default=[], metavar="FIELD=V",
                     help="per-call launch override (include/nsx_tune.h nsx_tune field), e.g. blocks_per_cu=2")
@@ -927,6 +941,47 @@ def load_traffic(config_id):
     return d
 
 
+DUMP_MAX_ELEMS = 4 << 20  # per array: 16 MiB of float32 (a step returns at most two arrays)
+DUMP_SAMPLE_SEED = 0x1D0
+
+
+def output_arrays(cfg, w) -> dict:
+    """What a caller of the timed entry point receives from one step, by name: the raw 16-bit sums
+    (`checksums`), the validity bitmask (`mask`), and for the sender pass the wire images (`wire`) as well."""
+    if cfg["kind"] == "tcp_build":
+        return {"checksums": w["out"], "wire": w["wire"]}
+    if cfg["kind"] == "rx" or cfg.get("mask"):
+        return {"mask": w["out"]}
+    return {"checksums": w["out"]}
+
+
+def dump_outputs(dirname, arrays, rank=0, world=1) -> list:
+    """--dump-outputs: each array of the last timed step as DIR/<name>.npy (rank r of several: <name>_rank<r>.npy)
+    in float32, exactly: bytes as they are, 16-bit sums as unsigned values, 64-bit mask words as their four 16-bit
+    quarters (little-endian order). An array of more than DUMP_MAX_ELEMS elements is written as a fixed sample of
+    that many: the elements at sorted(default_rng(DUMP_SAMPLE_SEED).integers(0, size, DUMP_MAX_ELEMS)), the same
+    positions in every run. Returns the files written."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    files = []
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).reshape(-1)
+        if t.dtype == torch.int64:
+            t = t.view(torch.int16)
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, t.numel(), DUMP_MAX_ELEMS))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        a = t.cpu().numpy()
+        if a.dtype == np.int16:
+            a = a.view(np.uint16)
+        assert a.dtype in (np.uint8, np.uint16), a.dtype  # exact in float32
+        path = os.path.join(dirname, name + (f"_rank{rank}" if world > 1 else "") + ".npy")
+        np.save(path, a.astype(np.float32))
+        files.append(path)
+    return files
+
+
 def dry_run(args) -> int:
     """--dry-run: the rank/launch/timing plumbing with the CPU oracle as each rank's step (no GPU)."""
     sys.path.insert(0, ROOT)
@@ -934,8 +989,13 @@ def dry_run(args) -> int:
     dist = Dist("gloo")
     n, L = 256, 1500
     buf = O.c_splitmix64(0x1071 + dist.rank, n * L)
-    wall, launch_ms, own = timed_loop(lambda: O.c_batch(buf, n, stride=L, seg_len=L, threads=1), lambda: None,
-                                      dist.barrier, args.steps, args.warmup)
+    last = {}
+
+    def step():
+        last["checksums"] = O.c_batch(buf, n, stride=L, seg_len=L, threads=1)
+    wall, launch_ms, own = timed_loop(step, lambda: None, dist.barrier, args.steps, args.warmup)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"checksums": last["checksums"].view("int16")}, dist.rank, dist.world)
     wall_max = dist.max(wall)
     idents = dist.gather({"host": socket.gethostname(), "local_device": None, "pci": None, "uuid": None,
                           "key": None})
@@ -954,16 +1014,26 @@ def dry_run(args) -> int:
     return 0
 
 
-def build_library() -> None:
+def build_library() -> str:
     """Bring libnsx_csum.so up to date before it is loaded (incremental make: a no-op when the pushed binary
-    matches its sources; ~35 s for a full rebuild). A failed build is an error, never a stale library."""
+    matches its sources; ~35 s for a full rebuild). A failed build is an error, never a stale library.
+    In a tree this user cannot write to (built and installed by someone else, or mounted read-only) nothing can be
+    built, so the library is loaded as it stands — loading fails if it is not there — and the line says so
+    (`library_build`). Returns that field's value."""
     import fcntl
-    with open(os.path.join(ROOT, "network-stack_amd", ".build.lock"), "w") as lk:
+    try:
+        lk = open(os.path.join(ROOT, "network-stack_amd", ".build.lock"), "w")
+    except OSError as e:  # EACCES / EROFS / EPERM
+        print(f"bench.py: network-stack_amd is not writable ({e.strerror}): loading the library as it is",
+              file=sys.stderr)
+        return "skipped: tree not writable"
+    with lk:
         fcntl.flock(lk, fcntl.LOCK_EX)
         r = subprocess.run(["make", "-s", "-j16", "-C", os.path.join(ROOT, "network-stack_amd")],
                            stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:
         raise SystemExit(f"bench.py: building network-stack_amd failed:\n{r.stdout[-4000:]}")
+    return "up to date (make)"
 
 
 def main(argv=None) -> int:
@@ -974,7 +1044,7 @@ def main(argv=None) -> int:
     # (torchrun … bench.py: WORLD_SIZE set, NSX_BENCH_BUILT not) — there the first rank to take the lock builds and
     # the others, waiting on it, find nothing to do, so no rank loads a stale or half-written library
     if not args.dry_run and not args.no_build and os.environ.get("NSX_BENCH_BUILT") != "1":
-        build_library()
+        os.environ["NSX_BENCH_LIBRARY_BUILD"] = build_library()
         os.environ["NSX_BENCH_BUILT"] = "1"
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args.gpus, argv)  # before anything touches a GPU
@@ -1038,8 +1108,10 @@ def main(argv=None) -> int:
     wall_max = dist.max(wall, device)
     stats = dist.gather({"rank": dist.rank, "device": "%s/%s" % (socket.gethostname(), devf["devices"][dist.rank]["pci"]),
                          "wall_s": wall, "own_s": own, "step_ms": launch_ms[0] if launch_ms else None})
+    if args.dump_outputs:  # the output buffers as the last timed step left them
+        dump_outputs(args.dump_outputs, output_arrays(cfg, w), dist.rank, dist.world)
     cpu = None
-    if dist.world == 1 and args.cpu_seconds > 0:
+    if args.full and dist.world == 1 and args.cpu_seconds > 0:
         cpu = cpu_baseline(cfg, w, args.cpu_seconds)
     line = result_line(world=dist.world, steps=args.steps, warmup=args.warmup, wall_max=wall_max,
                        bytes_per_rank_step=w["bytes"], units_total=cfg["n"] * dist.world, workload=cfg["name"],
@@ -1049,6 +1121,8 @@ def main(argv=None) -> int:
                            f"{args.config}n" if args.no_pseudo and WORKLOADS[args.config].get("pseudo") else args.config), metric=cfg.get("metric", METRIC),
                        launches=w.get("launches", 1), n_gpus=devf["n_gpus"], rank_stats=stats)
     line["backend"] = backend if dist.on else None
+    line["full"] = bool(args.full)
+    line["library_build"] = os.environ.get("NSX_BENCH_LIBRARY_BUILD", "skipped: --no-build or built by the launcher")
     line.update({k: v for k, v in devf.items() if k != "n_gpus"})
     if devf["distinct_devices"] < dist.world:  # gloo rehearsal: ranks share a GPU; n_gpus counts GPUs
         line["rehearsal"] = True

@@ -185,6 +185,80 @@ def test_cpu_baseline_rx_frames():
     assert not bench.cpu_baseline(cfg, w, 0.05)["sample_parity_vs_gpu"]
 
 
+def test_full_and_dump_outputs_options():
+    """A plain run skips the CPU baseline leg; --full asks for it. --dump-outputs names a directory."""
+    plain = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert not plain.full and plain.dump_outputs is None and plain.steps == 3 and plain.warmup == 1
+    full = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert full.full and full.dump_outputs == "d"
+
+
+def test_build_library_in_a_tree_it_cannot_write_to(tmp_path, monkeypatch, capfd):
+    """A benchmark run by a user who cannot write to the tree (someone else built it) builds nothing and loads the
+    library as it stands, saying so, instead of dying on its lock file."""
+    tree = tmp_path / "ro"
+    (tree / "network-stack_amd").mkdir(parents=True)
+    (tree / "network-stack_amd").chmod(0o555)
+    if os.access(tree / "network-stack_amd", os.W_OK):  # a superuser writes anywhere: no such directory instead
+        tree = tmp_path / "absent"
+    monkeypatch.setattr(bench, "ROOT", str(tree))
+    assert bench.build_library() == "skipped: tree not writable"
+    assert "not writable" in capfd.readouterr().err
+    assert not os.path.exists(tree / "network-stack_amd" / ".build.lock")
+
+
+def test_output_arrays_by_workload_kind():
+    w = {"out": object(), "wire": object()}
+    assert list(bench.output_arrays(bench.WORKLOADS[2], w)) == ["checksums"]
+    assert list(bench.output_arrays(bench.WORKLOADS[3], w)) == ["checksums"]
+    assert bench.output_arrays(bench.WORKLOADS[6], w) == {"checksums": w["out"], "wire": w["wire"]}
+    assert list(bench.output_arrays(bench.WORKLOADS[7], w)) == ["checksums"]
+    assert list(bench.output_arrays(bench.WORKLOADS[9], w)) == ["mask"]
+    assert list(bench.output_arrays(bench.WORKLOADS[10], w)) == ["mask"]
+
+
+def test_dump_outputs_exact_float32_and_fixed_sample(tmp_path, monkeypatch):
+    """Sums as unsigned 16-bit values, mask words as their four 16-bit quarters, bytes as they are; an array over
+    the element cap is written as the same seeded sample of positions every time."""
+    sums = np.array([0, 1, 0x7FFF, 0x8000, 0xFFFF], np.uint16)
+    words = np.array([0x0123456789ABCDEF, 0xFFFF000000008000], np.uint64)
+    wire = np.arange(256, dtype=np.uint8)
+    arrays = {"checksums": torch.from_numpy(sums.view(np.int16)), "mask": torch.from_numpy(words.view(np.int64)),
+              "wire": torch.from_numpy(wire)}
+    files = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    assert sorted(os.path.basename(f) for f in files) == ["checksums.npy", "mask.npy", "wire.npy"]
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in arrays}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(got["checksums"], sums.astype(np.float32))
+    assert np.array_equal(got["mask"], words.view(np.uint16).astype(np.float32))
+    assert np.array_equal(got["wire"], wire.astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 64)
+    big = torch.from_numpy(np.arange(1000, dtype=np.int16))
+    bench.dump_outputs(str(tmp_path / "b"), {"checksums": big}, rank=1, world=2)
+    bench.dump_outputs(str(tmp_path / "c"), {"checksums": big}, rank=1, world=2)
+    s = np.load(tmp_path / "b" / "checksums_rank1.npy")
+    idx = np.sort(np.random.default_rng(bench.DUMP_SAMPLE_SEED).integers(0, 1000, 64))
+    assert s.shape == (64,) and np.array_equal(s, idx.astype(np.float32))
+    assert np.array_equal(s, np.load(tmp_path / "c" / "checksums_rank1.npy"))
+
+
+def test_dry_run_dumps_the_last_steps_outputs(tmp_path):
+    """`--steps` sets the timed steps and the line carries ms_per_step; --dump-outputs writes the last step's sums,
+    the same from run to run (the inputs are seeded) and equal to the oracle's for that batch."""
+    outs = []
+    for d in ("a", "b"):
+        r = _bench("--gpus", "1", "--dry-run", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / d))
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+        assert line["cpu_baseline"] is None
+        assert os.listdir(tmp_path / d) == ["checksums.npy"]
+        outs.append(np.load(tmp_path / d / "checksums.npy"))
+    assert outs[0].dtype == np.float32 and np.array_equal(outs[0], outs[1])
+    want = O.c_batch(O.c_splitmix64(0x1071, 256 * 1500), 256, stride=1500, seg_len=1500)
+    assert np.array_equal(outs[0], want.astype(np.float32))
+
+
 def test_config2_pseudo_header_partials_in_the_workload_and_the_line():
     """config 2 (and 5) are measured over N x u32 pseudo-header partials, counted
     in the algorithmic bytes; --no-pseudo names the partial-less line and finds its own traffic profile."""

@@ -36,11 +36,11 @@ bench_args() {  # bench_args <workload> → bench.py arguments (Nn = workload N 
   local c=${1%n} extra=""
   [ "$c" != "$1" ] && extra="--no-pseudo"
   case $c in
-    2) echo "--config 2 $extra" ;;
-    3) echo "--config 3 --cpu-seconds 5 $extra" ;;
-    4|12) echo "--config $c --steps 50 --cpu-seconds 5 $extra" ;;
-    5) echo "--config 5 --steps 20 --cpu-seconds 0 $extra" ;;
-    *) echo "--config $c --steps 100 --cpu-seconds 5 $extra" ;;
+    2) echo "--config 2 --full $extra" ;;  # --full: the line's cpu_baseline leg
+    3) echo "--config 3 --full --cpu-seconds 5 $extra" ;;
+    4|12) echo "--config $c --steps 50 --full --cpu-seconds 5 $extra" ;;
+    5) echo "--config 5 --steps 20 $extra" ;;
+    *) echo "--config $c --steps 100 --full --cpu-seconds 5 $extra" ;;
   esac
 }
 case $mode in

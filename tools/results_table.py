@@ -6,7 +6,7 @@
 One row per workload: whole-job rate, kernel mean per launch, kernel rate and roofline fraction, HBM traffic over
 the algorithmic bytes (this round's profiles/traffic_config<W>.json if there is one, else the line's
 `roofline.traffic`), and the CPU
-baseline (the Go-faithful loop on the box's CPU share and on one thread)."""
+baseline (the Go-faithful loop on the box's CPU share and on one thread; in lines taken with `bench.py --full`)."""
 import glob
 import json
 import os
