@@ -192,6 +192,59 @@ uint64_t nsx_tcp_wire_len(uint64_t opt_len, uint64_t data_len);
  * nullable): h_out_off[i] = Σ_{j<i} round_up4(wire_len_j), h_out_off[n] = total. */
 int nsx_tcp_layout_host(const uint64_t* h_opt_off, const uint64_t* h_data_off, uint64_t n, uint64_t* h_out_off);
 
+/* Fused transmit pass (the transmit twin of the receive passes below, SURVEY.md
+ * §8 f1 + f2 + f3 in one launch): whole IPv4 / IPv6 datagrams carrying TCP,
+ * built from the segment fields plus the per-frame IP fields of nsx_ip_hdr_soa
+ * (device arrays; src / dst as ip.Addr.Raw(), network/ip/v4/ipv4.go:15,
+ * v6/ipv6.go:16). Frame i is written at d_out + d_out_off[i]. Its TCP part is
+ * exactly the image nsx_tcp_build_dev writes (fields, options, the reference's
+ * padding, payload; a NULL `offset` computed on the device); let wire be
+ * nsx_tcp_wire_len of it.
+ *   IPv4: 20 header bytes (no IP options) then the image: 0x45, 0x00, total
+ *     length 20 + wire, ident, 0x40 0x00 (DF, offset 0), ttl, 6
+ *     (ip.NextProtoTCP, network/ip/protocols.go:8), the header checksum (~raw
+ *     over the 20 bytes with the field zero, RFC 791 §3.1), src, dst.
+ *   IPv6: the 40-byte fixed header of RFC 8200 §3 then the image: version 6,
+ *     tclass, flow, payload length wire, Next Header 6, hop limit ttl, src, dst.
+ * The TCP checksum field is ~raw, raw being the computeChecksum sum
+ * (tcp.go:72-95) over the pseudo-header ‖ the image with the field zero; the
+ * pseudo-header is built from the frame's own src / dst, protocol 6 and wire
+ * (RFC 9293 §3.1, 12 bytes; RFC 8200 §8.1, 40 bytes) — there is no partials
+ * argument and no second launch. d_tcp_raw (nullable) receives raw.
+ * Layout rule as nsx_tcp_build_dev: d_out_off[i] a multiple of 4 with room for
+ * the frame rounded up to 4 bytes, the up to 3 bytes after a frame zero-filled,
+ * bytes between a padded frame and the next offset left as they were.
+ * nsx_tx_layout_host makes packed offsets, h_out_off[i] = Σ_{j<i}
+ * round_up4(ip_hdr_len + wire_j), ip_hdr_len 20 or 40 (NSX_EINVAL otherwise).
+ * When every frame length is a multiple of 4 and the layout is packed,
+ * d_out_off is directly the d_offsets of nsx_rx_ipv4_tcp_verify_dev /
+ * nsx_rx_ipv6_tcp_verify_dev over d_out.
+ * A frame whose length does not fit its 16-bit length field (IPv4 wire > 65515,
+ * IPv6 wire > 65535) is not built: nothing is written for it, padding included,
+ * and d_tcp_raw[i] = 0 (a built frame's raw sum is never 0: the pseudo-header
+ * holds the byte 6). Validation and conventions as nsx_tcp_build_dev; no
+ * allocation, no host sync, no per-stream counters: the call can be captured
+ * into a graph. */
+typedef struct {
+    const uint8_t*  src;     /* n×4 (IPv4) or n×16 (IPv6) bytes, ip.Addr.Raw() */
+    const uint8_t*  dst;
+    const uint16_t* ident;   /* IPv4 identification; NULL = 0; ignored for IPv6 */
+    const uint8_t*  ttl;     /* TTL / hop limit; NULL = 64 */
+    const uint8_t*  tclass;  /* IPv6 traffic class; NULL = 0; ignored for IPv4 (TOS = 0) */
+    const uint32_t* flow;    /* IPv6 flow label (low 20 bits); NULL = 0; ignored for IPv4 */
+} nsx_ip_hdr_soa;
+
+int nsx_tx_ipv4_tcp_build_dev(const nsx_ip_hdr_soa* ip, const nsx_tcp_hdr_soa* tcp, const uint8_t* d_opts,
+                              const uint64_t* d_opt_off, const uint8_t* d_data, const uint64_t* d_data_off,
+                              uint64_t data_bytes, uint64_t n, uint8_t* d_out, const uint64_t* d_out_off,
+                              uint16_t* d_tcp_raw, nsx_stream_t stream);
+int nsx_tx_ipv6_tcp_build_dev(const nsx_ip_hdr_soa* ip, const nsx_tcp_hdr_soa* tcp, const uint8_t* d_opts,
+                              const uint64_t* d_opt_off, const uint8_t* d_data, const uint64_t* d_data_off,
+                              uint64_t data_bytes, uint64_t n, uint8_t* d_out, const uint64_t* d_out_off,
+                              uint16_t* d_tcp_raw, nsx_stream_t stream);
+int nsx_tx_layout_host(const uint64_t* h_opt_off, const uint64_t* h_data_off, uint64_t n, uint32_t ip_hdr_len,
+                       uint64_t* h_out_off);
+
 /* IPv4 header checksums (RFC 791 §3.1; SURVEY.md §8 f3 — the reference has no
  * IPv4 header codec, network/ip/v4/ipv4.go holds addresses only). Packet i's
  * header starts at d_base + i*stride + hdr_off (any alignment) and is IHL*4
@@ -306,6 +359,22 @@ int nsx_rx_ipv6_tcp_verify_host(const uint8_t* h_base, const uint64_t* h_offsets
 int nsx_tcp_build_host(const nsx_tcp_hdr_soa* h_hdr, const uint8_t* h_opts, const uint64_t* h_opt_off,
                        const uint8_t* h_data, const uint64_t* h_data_off, const uint32_t* h_prefix_partial,
                        uint64_t n, uint8_t* h_out, const uint64_t* h_out_off, uint16_t* h_raw, int num_gpus);
+
+/* The fused transmit pass (nsx_tx_ipv4_tcp_build_dev / nsx_tx_ipv6_tcp_build_dev)
+ * over host-resident inputs: nsx_tcp_build_host with the nsx_ip_hdr_soa arrays
+ * (HOST arrays here) staged alongside the TCP fields, same chunks, shards and
+ * layout rule, whole datagrams written to h_out + h_out_off[i] and the TCP raw
+ * sums to h_tcp_raw (nullable). A batch holding a frame that does not fit its
+ * IP length field (IPv4 wire > 65515, IPv6 wire > 65535) is NSX_EINVAL, checked
+ * with the offsets before any copy. */
+int nsx_tx_ipv4_tcp_build_host(const nsx_ip_hdr_soa* h_ip, const nsx_tcp_hdr_soa* h_tcp, const uint8_t* h_opts,
+                               const uint64_t* h_opt_off, const uint8_t* h_data, const uint64_t* h_data_off,
+                               uint64_t n, uint8_t* h_out, const uint64_t* h_out_off, uint16_t* h_tcp_raw,
+                               int num_gpus);
+int nsx_tx_ipv6_tcp_build_host(const nsx_ip_hdr_soa* h_ip, const nsx_tcp_hdr_soa* h_tcp, const uint8_t* h_opts,
+                               const uint64_t* h_opt_off, const uint8_t* h_data, const uint64_t* h_data_off,
+                               uint64_t n, uint8_t* h_out, const uint64_t* h_out_off, uint16_t* h_tcp_raw,
+                               int num_gpus);
 
 /* The host batch calls keep per-device streams and grow-only device/pinned
  * staging buffers across calls (a transport calls them once per batch). This

@@ -115,7 +115,6 @@ int nsx_tcp_build_host_tuned(const nsx_tcp_hdr_soa* h_hdr, const uint8_t* h_opts
                              const uint8_t* h_data, const uint64_t* h_data_off, const uint32_t* h_prefix_partial,
                              uint64_t n, uint8_t* h_out, const uint64_t* h_out_off, uint16_t* h_raw, int num_gpus,
                              const nsx_tune* tune);
-
 /* Kernel launches one nsx_csum_fixed_dev(_tuned) call makes for this batch on the current device (its
  * back-to-back windows; 1 for most batches), for per-launch timing in benchmarks. */
 int nsx_fixed_launch_count(uint64_t stride, uint32_t seg_len, uint64_t n, const nsx_tune* tune, uint64_t* out_count);
@@ -131,4 +130,9 @@ int nsx_deal_sets_in_use(uint32_t* out_count);
 #ifdef __cplusplus
 }
 #endif
+
+/* The _tuned twins of the fused transmit pass (nsx_tx_*): declared in a header of their own, which this one
+ * brings in. */
+#include "nsx_tx_tune.h"
+
 #endif /* NSX_TUNE_H */

@@ -311,9 +311,74 @@ int nsx_tcp_build_dev_tuned(const nsx_tcp_hdr_soa* hdr, const uint8_t* d_opts, c
     if (dev < 0) return NSX_ENODEV;
     const nsx::TcpHdrSoA h{hdr->src_port, hdr->dst_port, hdr->seq_num, hdr->ack_num,
                            hdr->offset,   hdr->control,  hdr->window,  hdr->urgent_ptr};
-    return map_err(nsx::launch_tcp_build(make_cfg(dev, tune), h, d_opts, d_opt_off, d_data, d_data_off, data_bytes,
-                                         d_prefix_partial, n, d_out, d_out_off, d_raw,
+    return map_err(nsx::launch_tcp_build(make_cfg(dev, tune), 0, nullptr, h, d_opts, d_opt_off, d_data, d_data_off,
+                                         data_bytes, d_prefix_partial, n, d_out, d_out_off, d_raw,
                                          static_cast<hipStream_t>(stream)));
+}
+
+int nsx_tx_layout_host(const uint64_t* h_opt_off, const uint64_t* h_data_off, uint64_t n, uint32_t ip_hdr_len,
+                       uint64_t* h_out_off) {
+    if ((ip_hdr_len != 20 && ip_hdr_len != 40) || !h_out_off || (n && !h_data_off)) return NSX_EINVAL;
+    uint64_t at = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        h_out_off[i] = at;
+        const uint64_t ol = h_opt_off ? h_opt_off[i + 1] - h_opt_off[i] : 0;
+        at += (ip_hdr_len + nsx_tcp_wire_len(ol, h_data_off[i + 1] - h_data_off[i]) + 3) & ~3ull;
+    }
+    h_out_off[n] = at;
+    return NSX_OK;
+}
+
+// The fused transmit pass: nsx_tcp_build_dev's validation plus the IP fields', then the same launcher.
+static int tx_build_dev(int ipver, const nsx_ip_hdr_soa* ip, const nsx_tcp_hdr_soa* hdr, const uint8_t* d_opts,
+                        const uint64_t* d_opt_off, const uint8_t* d_data, const uint64_t* d_data_off,
+                        uint64_t data_bytes, uint64_t n, uint8_t* d_out, const uint64_t* d_out_off,
+                        uint16_t* d_tcp_raw, nsx_stream_t stream, const nsx_tune* tune) {
+    if (n == 0) return NSX_OK;
+    if (!ip || !ip->src || !ip->dst || !hdr || !hdr->src_port || !hdr->dst_port || !hdr->seq_num || !hdr->ack_num ||
+        !hdr->control || !hdr->window || !hdr->urgent_ptr || !d_data_off || !d_out || !d_out_off ||
+        (d_opt_off && !d_opts) || (data_bytes && !d_data))
+        return NSX_EINVAL;
+    const int dev = current_device();
+    if (dev < 0) return NSX_ENODEV;
+    const nsx::IpHdrSoA a{ip->src, ip->dst, ip->ident, ip->ttl, ip->tclass, ip->flow};
+    const nsx::TcpHdrSoA h{hdr->src_port, hdr->dst_port, hdr->seq_num, hdr->ack_num,
+                           hdr->offset,   hdr->control,  hdr->window,  hdr->urgent_ptr};
+    return map_err(nsx::launch_tcp_build(make_cfg(dev, tune), ipver, &a, h, d_opts, d_opt_off, d_data, d_data_off,
+                                         data_bytes, nullptr, n, d_out, d_out_off, d_tcp_raw,
+                                         static_cast<hipStream_t>(stream)));
+}
+
+int nsx_tx_ipv4_tcp_build_dev(const nsx_ip_hdr_soa* ip, const nsx_tcp_hdr_soa* tcp, const uint8_t* d_opts,
+                              const uint64_t* d_opt_off, const uint8_t* d_data, const uint64_t* d_data_off,
+                              uint64_t data_bytes, uint64_t n, uint8_t* d_out, const uint64_t* d_out_off,
+                              uint16_t* d_tcp_raw, nsx_stream_t stream) {
+    return tx_build_dev(4, ip, tcp, d_opts, d_opt_off, d_data, d_data_off, data_bytes, n, d_out, d_out_off, d_tcp_raw,
+                        stream, nullptr);
+}
+
+int nsx_tx_ipv4_tcp_build_dev_tuned(const nsx_ip_hdr_soa* ip, const nsx_tcp_hdr_soa* tcp, const uint8_t* d_opts,
+                                    const uint64_t* d_opt_off, const uint8_t* d_data, const uint64_t* d_data_off,
+                                    uint64_t data_bytes, uint64_t n, uint8_t* d_out, const uint64_t* d_out_off,
+                                    uint16_t* d_tcp_raw, nsx_stream_t stream, const nsx_tune* tune) {
+    return tx_build_dev(4, ip, tcp, d_opts, d_opt_off, d_data, d_data_off, data_bytes, n, d_out, d_out_off, d_tcp_raw,
+                        stream, tune);
+}
+
+int nsx_tx_ipv6_tcp_build_dev(const nsx_ip_hdr_soa* ip, const nsx_tcp_hdr_soa* tcp, const uint8_t* d_opts,
+                              const uint64_t* d_opt_off, const uint8_t* d_data, const uint64_t* d_data_off,
+                              uint64_t data_bytes, uint64_t n, uint8_t* d_out, const uint64_t* d_out_off,
+                              uint16_t* d_tcp_raw, nsx_stream_t stream) {
+    return tx_build_dev(6, ip, tcp, d_opts, d_opt_off, d_data, d_data_off, data_bytes, n, d_out, d_out_off, d_tcp_raw,
+                        stream, nullptr);
+}
+
+int nsx_tx_ipv6_tcp_build_dev_tuned(const nsx_ip_hdr_soa* ip, const nsx_tcp_hdr_soa* tcp, const uint8_t* d_opts,
+                                    const uint64_t* d_opt_off, const uint8_t* d_data, const uint64_t* d_data_off,
+                                    uint64_t data_bytes, uint64_t n, uint8_t* d_out, const uint64_t* d_out_off,
+                                    uint16_t* d_tcp_raw, nsx_stream_t stream, const nsx_tune* tune) {
+    return tx_build_dev(6, ip, tcp, d_opts, d_opt_off, d_data, d_data_off, data_bytes, n, d_out, d_out_off, d_tcp_raw,
+                        stream, tune);
 }
 
 int nsx_tcp_parse_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n, const nsx_tcp_parsed_soa* out,

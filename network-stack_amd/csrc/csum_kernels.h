@@ -61,10 +61,19 @@ struct TcpHdrSoA {  // device arrays, one entry per segment (tcp.go:39-54 field 
     const uint16_t* window;
     const uint16_t* urgent;
 };
-hipError_t launch_tcp_build(const LaunchCfg& c, const TcpHdrSoA& h, const uint8_t* opts, const uint64_t* opt_off,
-                            const uint8_t* data, const uint64_t* data_off, uint64_t data_bytes,
-                            const uint32_t* partial, uint64_t n, uint8_t* out, const uint64_t* out_off,
-                            uint16_t* raw, hipStream_t st);
+struct IpHdrSoA {  // device arrays of the transmit pass, one entry per frame (include/nsx_csum.h nsx_ip_hdr_soa)
+    const uint8_t* src;
+    const uint8_t* dst;
+    const uint16_t* ident;
+    const uint8_t* ttl;
+    const uint8_t* tclass;
+    const uint32_t* flow;
+};
+// TCP wire images (ip null), or whole IPv4 / IPv6 datagrams (ipver 4 / 6: ip's fields, partial unused).
+hipError_t launch_tcp_build(const LaunchCfg& c, int ipver, const IpHdrSoA* ip, const TcpHdrSoA& h,
+                            const uint8_t* opts, const uint64_t* opt_off, const uint8_t* data,
+                            const uint64_t* data_off, uint64_t data_bytes, const uint32_t* partial, uint64_t n,
+                            uint8_t* out, const uint64_t* out_off, uint16_t* raw, hipStream_t st);
 struct TcpParsedSoA {  // device arrays, one entry per segment; every member nullable
     uint16_t* src_port;
     uint16_t* dst_port;

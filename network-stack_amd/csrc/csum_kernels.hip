@@ -2829,6 +2829,7 @@ struct BuildSeg {  // wave-uniform description of one segment
     int32_t sh0;                  // payload source offset (from the descriptor base) = wire pos + sh0
     uint64_t ob, db;              // option / payload byte offsets
     bool fast;                    // no options, payload 4-aligned, whole dwords, ≥ 20 B into the data array
+    uint32_t I[10];               // transmit pass only: the IP header dwords as stored (5 IPv4, 10 IPv6)
 };
 
 // Source row r: 4+1 dwords per lane. Row 0 (head) clamps each dword separately.
@@ -2858,26 +2859,29 @@ __device__ __forceinline__ void build_load_body(__amdgpu_buffer_rsrc_t drs, cons
 // ending at the last option dword; five dword loads per lane (index pos0/4 - 5 + j, negative or past the
 // options: out of range, 0, no traffic), realigned by ob & 3 and masked to the option bytes, so the header
 // padding (tcp.go:118-121) reads 0. Issue (opt_load) and compose (opt_fin) are split so that the loads go
-// out with the payload's.
+// out with the payload's. IPH: the transmit pass's IP header length, by which every position moves up.
 struct OptRaw {
     u32x4 lo;
     uint32_t hi;
 };
 
+template <int IPH = 0>
 __device__ __forceinline__ OptRaw opt_load(const uint8_t* __restrict__ opts, uint64_t ob, uint32_t optlen,
                                            uint32_t pos0) {
     const __amdgpu_buffer_rsrc_t rs = make_rsrc(opts + (ob & ~3ull), ((ob & 3u) + optlen + 3u) & ~3u);
-    const int32_t t = (int32_t)(pos0 >> 2) - 5;
+    const int32_t t = (int32_t)(pos0 >> 2) - (5 + IPH / 4);
     uint32_t d[5];
 #pragma unroll
     for (int j = 0; j < 5; ++j) d[j] = __builtin_amdgcn_raw_buffer_load_b32(rs, t + j >= 0 ? (uint32_t)(t + j) * 4u : kOOB, 0, 0);
     return OptRaw{u32x4{d[0], d[1], d[2], d[3]}, d[4]};
 }
 
+template <int IPH = 0>
 __device__ __forceinline__ u32x4 opt_fin(OptRaw o, uint64_t ob, uint32_t optlen, uint32_t pos0) {
     const uint32_t sh = (uint32_t)ob & 3u;
     const u32x4 x = sh ? realign(o.lo, o.hi, sh) : o.lo;
-    return keep_bytes(x, min(max(20 - (int32_t)pos0, 0), 16), min(max(20 + (int32_t)optlen - (int32_t)pos0, 0), 16));
+    return keep_bytes(x, min(max(IPH + 20 - (int32_t)pos0, 0), 16),
+                      min(max(IPH + 20 + (int32_t)optlen - (int32_t)pos0, 0), 16));
 }
 
 // Staged options: when every segment of a wave's group has ≤ 40 option bytes (all valid TCP: data offset ≤ 15),
@@ -2895,7 +2899,7 @@ __device__ __forceinline__ void set_comp(u32x4& x, int c, uint32_t v, bool on) {
     if (c == 3) x.w = on ? v : x.w;
 }
 
-template <bool REPLACE>
+template <bool REPLACE, int IPH = 0>
 __device__ __forceinline__ u32x4 staged_opts(const uint32_t (&od)[kOptDw], uint32_t k, uint32_t ndw, uint32_t lane,
                                              u32x4 x) {
     if (!REPLACE) x = u32x4{0u, 0u, 0u, 0u};
@@ -2903,13 +2907,46 @@ __device__ __forceinline__ u32x4 staged_opts(const uint32_t (&od)[kOptDw], uint3
     for (int m = 0; m < kOptDw; ++m) {
         if ((uint32_t)m < ndw) {  // wave-uniform
             const uint32_t v = __builtin_amdgcn_readlane(od[m], k);
-            set_comp(x, (5 + m) & 3, v, lane == (uint32_t)((5 + m) >> 2));
+            set_comp(x, (IPH / 4 + 5 + m) & 3, v, lane == (uint32_t)((IPH / 4 + 5 + m) >> 2));
         }
     }
     return x;
 }
 
+// Transmit pass (IPH = 20 IPv4, 40 IPv6; 0 = the plain TCP build): the IP header's IPH/4 dwords sit ahead of
+// the TCP header, so frame dword d < IPH/4 is S.I[d], dwords IPH/4 .. IPH/4+4 are D0-D4 and every TCP-image
+// position moves up by IPH bytes — a multiple of 4, so dword alignment and the realign shift are unchanged.
+// hdr_end and wire of a BuildSeg are frame positions (IPH included). Dword d is component d % 4 of lane d / 4
+// in row 0. REPLACE: overwrite (the fast compositions, source bytes lie under the header); else OR into bytes
+// already masked to 0 (compose_row).
+template <int IPH, bool REPLACE>
+__device__ __forceinline__ void put_headers(u32x4& x, const BuildSeg& S, uint32_t lane) {
+    constexpr int kD = IPH / 4;
+#pragma unroll
+    for (int d = 0; d < kD + 5; ++d) {
+        const int t = d - kD;
+        const uint32_t v = t < 0 ? S.I[d < kD ? d : 0] : t == 0 ? S.D0 : t == 1 ? S.D1 : t == 2 ? S.D2 : t == 3 ? S.D3 : S.D4;
+        const bool on = lane == (uint32_t)(d >> 2);
+        if (REPLACE) {
+            set_comp(x, d & 3, v, on);
+        } else {
+            const uint32_t o = on ? v : 0u;
+            if ((d & 3) == 0) x.x |= o;
+            if ((d & 3) == 1) x.y |= o;
+            if ((d & 3) == 2) x.z |= o;
+            if ((d & 3) == 3) x.w |= o;
+        }
+    }
+}
+
+// The chunk holding the checksum dword (frame dword IPH/4 + 4): lane, component, byte position.
+template <int IPH>
+struct FieldAt {
+    static constexpr uint32_t lane = (IPH / 4 + 4) >> 2, comp = (IPH / 4 + 4) & 3, pos = IPH + 16;
+};
+
 // Compose row r of the wire image (general composition); oc = the chunk's option bytes (opt_fin, 0 when none).
+template <int IPH = 0>
 __device__ __forceinline__ u32x4 compose_row(const BuildSeg& S, u32x4 oc, uint32_t lane, uint32_t r, u32x4 lo,
                                              uint32_t hi) {
     const uint32_t pos0 = r * kRow + lane * 16u;
@@ -2918,10 +2955,14 @@ __device__ __forceinline__ u32x4 compose_row(const BuildSeg& S, u32x4 oc, uint32
         x = keep_bytes(x, min(max((int32_t)S.hdr_end - (int32_t)pos0, 0), 16),
                        min(max((int32_t)S.wire - (int32_t)pos0, 0), 16));
     if (r == 0) {  // header bytes 0-19
-        x.x |= lane == 0 ? S.D0 : lane == 1 ? S.D4 : 0u;
-        x.y |= lane == 0 ? S.D1 : 0u;
-        x.z |= lane == 0 ? S.D2 : 0u;
-        x.w |= lane == 0 ? S.D3 : 0u;
+        if constexpr (IPH == 0) {
+            x.x |= lane == 0 ? S.D0 : lane == 1 ? S.D4 : 0u;
+            x.y |= lane == 0 ? S.D1 : 0u;
+            x.z |= lane == 0 ? S.D2 : 0u;
+            x.w |= lane == 0 ? S.D3 : 0u;
+        } else {
+            put_headers<IPH, false>(x, S, lane);
+        }
     }
     x.x |= oc.x, x.y |= oc.y, x.z |= oc.z, x.w |= oc.w;  // option bytes [20, 20 + optlen)
     return x;
@@ -2929,23 +2970,61 @@ __device__ __forceinline__ u32x4 compose_row(const BuildSeg& S, u32x4 oc, uint32
 
 // Images of more than 2 rows (unpipelined path): compose, sum and store row r as it goes; dword 4 (urgent
 // pointer + checksum field) is held back and written with the field once the sum is known.
-template <int SP>
+// Store the chunk at pos0 of row r, holding back the dword with the checksum field: that chunk's other three
+// dwords go out now (IPH 0: dwords 5-7; 20: dwords 8, 10, 11; 40: dwords 12, 13, 15).
+template <int IPH, int SP>
+__device__ __forceinline__ void store_held(u32x4 x, __amdgpu_buffer_rsrc_t ors, uint32_t lane, uint32_t r,
+                                           uint32_t pos0) {
+    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+    typedef uint32_t v3u __attribute__((ext_vector_type(3)));
+    typedef uint32_t v2u __attribute__((ext_vector_type(2)));
+    using F = FieldAt<IPH>;
+    const bool d4 = r == 0 && lane == F::lane;  // this chunk holds the field's dword: store its other three now
+    __builtin_amdgcn_raw_buffer_store_b128(v4u{x.x, x.y, x.z, x.w}, ors, d4 ? kOOB : pos0, 0, SP);
+    if (r == 0) {
+        constexpr uint32_t c0 = F::lane * 16u;
+        if constexpr (F::comp == 0) {
+            __builtin_amdgcn_raw_buffer_store_b96(v3u{x.y, x.z, x.w}, ors, d4 ? c0 + 4u : kOOB, 0, SP);
+        } else if constexpr (F::comp == 1) {
+            __builtin_amdgcn_raw_buffer_store_b32(x.x, ors, d4 ? c0 : kOOB, 0, SP);
+            __builtin_amdgcn_raw_buffer_store_b64(v2u{x.z, x.w}, ors, d4 ? c0 + 8u : kOOB, 0, SP);
+        } else {
+            static_assert(F::comp == 2, "IPH is 0, 20 or 40");
+            __builtin_amdgcn_raw_buffer_store_b64(v2u{x.x, x.y}, ors, d4 ? c0 : kOOB, 0, SP);
+            __builtin_amdgcn_raw_buffer_store_b32(x.w, ors, d4 ? c0 + 12u : kOOB, 0, SP);
+        }
+    }
+}
+
+template <int SP, int IPH = 0>
 __device__ __forceinline__ uint32_t build_row(const BuildSeg& S, __amdgpu_buffer_rsrc_t ors, u32x4 oc, uint32_t lane,
                                               uint32_t r, u32x4 lo, uint32_t hi, uint32_t acc) {
     const uint32_t pos0 = r * kRow + lane * 16u;
-    const u32x4 x = compose_row(S, oc, lane, r, lo, hi);
+    const u32x4 x = compose_row<IPH>(S, oc, lane, r, lo, hi);
     acc = sad4(x, acc);
-    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-    typedef uint32_t v3u __attribute__((ext_vector_type(3)));
-    const bool d4 = r == 0 && lane == 1;  // this chunk holds dword 4: store its other three now
-    __builtin_amdgcn_raw_buffer_store_b128(v4u{x.x, x.y, x.z, x.w}, ors, d4 ? kOOB : pos0, 0, SP);
-    if (r == 0) __builtin_amdgcn_raw_buffer_store_b96(v3u{x.y, x.z, x.w}, ors, d4 ? 20u : kOOB, 0, SP);
+    store_held<IPH, SP>(x, ors, lane, r, pos0);
     return acc;
 }
 
 // PS: segments per register set on the pipelined fast-group path; OPT: the batch has an option array (else
 // every option branch compiles out: 61 VGPRs vs 120 at PS 2)
-template <int LP, int SP, int PS, bool OPT>
+//
+// IPH: the fused transmit pass (nsx_tx_ipv4_tcp_build_dev / nsx_tx_ipv6_tcp_build_dev) — the same pass writing
+// whole IPv4 (IPH 20) or IPv6 (IPH 40) datagrams: lane j also loads frame g0+j's addresses and IP fields and builds its IP header dwords,
+// the IPv4 header checksum and the pseudo-header partial in the metadata phase; the header dwords then ride
+// with D0-D4 (put_headers). The wave sums every frame dword, IP header included, and the lane's partial makes
+// up the difference: an IPv4 header with its checksum in place sums to 0xFFFF ≡ 0, so the partial is the
+// pseudo-header's (RFC 9293 §3.1: addresses + 6 + TCP length); an IPv6 header shares its addresses and
+// payload length with the pseudo-header (RFC 8200 §8.1), so the partial is the pseudo-header's sum less the
+// header's: 6 − (version/class/flow words) − (next header, hop limit word), in one's complement. The raw sum
+// is nonzero either way (the byte 6), so it is the same representative the serial loop reaches. No partials
+// array is read (`partial` is null). IPH 0 compiles to the TCP build unchanged (`ip` is empty).
+template <int IPH>
+struct IpArgs : IpHdrSoA {};
+template <>
+struct IpArgs<0> {};  // the TCP build takes no IP fields: an empty trailing argument
+
+template <int LP, int SP, int PS, bool OPT, int IPH = 0>
 __global__ __launch_bounds__(kBlock) void tcp_build_kernel(TcpHdrSoA h, const uint8_t* __restrict__ opts,
                                                            const uint64_t* __restrict__ opt_off,
                                                            const uint8_t* __restrict__ data,
@@ -2954,9 +3033,11 @@ __global__ __launch_bounds__(kBlock) void tcp_build_kernel(TcpHdrSoA h, const ui
                                                            uint8_t* __restrict__ out,
                                                            const uint64_t* __restrict__ out_off,
                                                            uint16_t* __restrict__ raw_out, uint32_t group,
-                                                           uint32_t clog, int pipe) {
+                                                           uint32_t clog, int pipe, IpArgs<IPH> ip) {
+    static_assert(IPH == 0 || IPH == 20 || IPH == 40, "TCP images, IPv4 or IPv6 datagrams");
     typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-    typedef uint32_t v3u __attribute__((ext_vector_type(3)));
+    constexpr int kIpDw = IPH / 4;
+    using F = FieldAt<IPH>;
     const uint32_t lane = threadIdx.x & (kWave - 1);
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     const uint64_t data_end4 = (data_bytes + 3) & ~3ull;  // the last payload dword reads whole
@@ -2979,9 +3060,47 @@ __global__ __launch_bounds__(kBlock) void tcp_build_kernel(TcpHdrSoA h, const ui
         const uint32_t mD3 = moff | ((uint32_t)h.ctl[i] << 8) | (bswap16u(h.window[i]) << 16);
         const uint32_t mD4 = bswap16u(h.urgent[i]) << 16;  // checksum field (bytes 16-17) = 0 for the sum
         const uint64_t mdb = data_off[i], mde = data_off[i + 1], moo = out_off[i];
-        const uint32_t mpart = partial ? partial[i] : 0u;
-        const uint32_t mhdr = 20u + moptlen + (moptlen ? (20u + moptlen) % 4u : 0u);  // tcp.go:118-121
-        const uint32_t mwire = mhdr + (uint32_t)(mde - mdb);                             // < 2^31
+        uint32_t mpart = partial ? partial[i] : 0u;
+        // frame positions: IPH ahead of the TCP header
+        const uint32_t mhdr = IPH + 20u + moptlen + (moptlen ? (20u + moptlen) % 4u : 0u);  // tcp.go:118-121
+        const uint32_t mwire = mhdr + (uint32_t)(mde - mdb);                                   // < 2^31
+        uint32_t mI[kIpDw ? kIpDw : 1];
+        uint32_t mskip = 0;  // the TCP length does not fit the IP length field: the frame is not built
+        if constexpr (IPH != 0) {
+            const uint64_t tlen = (uint64_t)(mhdr - IPH) + (mde - mdb);
+            mskip = tlen > (IPH == 20 ? 65515u : 65535u);
+            const uint32_t tl = (uint32_t)tlen & 0xFFFFu;
+            const uint32_t ttl = ip.ttl ? (uint32_t)ip.ttl[i] : 64u;
+            const bool al = (((uintptr_t)ip.src | (uintptr_t)ip.dst) & 3u) == 0;  // wave-uniform
+            constexpr int kA = IPH == 20 ? 1 : 4;                                 // dwords per address
+            uint32_t a[2 * kA];
+#pragma unroll
+            for (int w = 0; w < 2 * kA; ++w) {
+                const uint8_t* q = (w < kA ? ip.src : ip.dst) + (uint64_t)(4 * kA) * i + 4 * (w % kA);
+                a[w] = al ? *reinterpret_cast<const uint32_t*>(q)
+                          : (uint32_t)q[0] | (uint32_t)q[1] << 8 | (uint32_t)q[2] << 16 | (uint32_t)q[3] << 24;
+            }
+            if constexpr (IPH == 20) {
+                mI[0] = 0x45u | (bswap16u(20u + tl) << 16);
+                mI[1] = (ip.ident ? bswap16u(ip.ident[i]) : 0u) | (0x40u << 16);  // DF, fragment offset 0
+                mI[2] = ttl | (6u << 8);
+                mI[3] = a[0], mI[4] = a[1];
+                uint32_t hs = 0, as = 0;  // LE half-sums: the header with its field 0; the addresses
+#pragma unroll
+                for (int d = 0; d < 3; ++d) hs = __builtin_amdgcn_sad_u16(mI[d], 0u, hs);
+                as = __builtin_amdgcn_sad_u16(a[1], 0u, __builtin_amdgcn_sad_u16(a[0], 0u, 0u));
+                mI[2] |= (~fold32(hs + as) & 0xFFFFu) << 16;  // RFC 791 §3.1; the header starts even: LE half = swapped BE
+                mpart = bswap16u(fold32(as)) + 6u + tl;
+            } else {
+                const uint32_t vtf = (6u << 28) | ((ip.tclass ? (uint32_t)ip.tclass[i] : 0u) << 20) |
+                                     ((ip.flow ? ip.flow[i] : 0u) & 0xFFFFFu);
+                mI[0] = bswap32u(vtf);
+                mI[1] = bswap16u(tl) | (6u << 16) | (ttl << 24);
+#pragma unroll
+                for (int w = 0; w < 8; ++w) mI[2 + w] = a[w];
+                mpart = 6u + (0xFFFFu - (0x0600u | ttl)) + (0xFFFFu - (vtf >> 16)) + (0xFFFFu - (vtf & 0xFFFFu));
+            }
+        }
         uint32_t od[kOptDw];
         bool staged = false;  // wave-uniform: the group's options are held in od (see staged_opts)
         if (OPT) {
@@ -3014,6 +3133,8 @@ __global__ __launch_bounds__(kBlock) void tcp_build_kernel(TcpHdrSoA h, const ui
             S.optlen = __builtin_amdgcn_readlane(moptlen, k);
             S.hdr_end = __builtin_amdgcn_readlane(mhdr, k);
             S.wire = __builtin_amdgcn_readlane(mwire, k);
+#pragma unroll
+            for (int d = 0; d < kIpDw; ++d) S.I[d] = __builtin_amdgcn_readlane(mI[d], k);
             S.nb4 = (S.wire + 3u) & ~3u;
             S.rows = (S.nb4 + kRow - 1) / kRow;
             S.ob = readlane64(mob, k);
@@ -3037,7 +3158,7 @@ __global__ __launch_bounds__(kBlock) void tcp_build_kernel(TcpHdrSoA h, const ui
         };
         auto seg_done = [&](uint32_t k, const BuildSeg& S, __amdgpu_buffer_rsrc_t ors, uint32_t acc) {
             const uint32_t raw = seg_raw(k, acc);
-            __builtin_amdgcn_raw_buffer_store_b32(S.D4 | bswap16u(~raw & 0xFFFFu), ors, lane == 0 ? 16u : kOOB, 0, SP);
+            __builtin_amdgcn_raw_buffer_store_b32(S.D4 | bswap16u(~raw & 0xFFFFu), ors, lane == 0 ? F::pos : kOOB, 0, SP);
         };
         auto flush_raws = [&]() {
             const __amdgpu_buffer_rsrc_t rrs = make_rsrc(raw_out + g0, raw_out ? (uint64_t)cnt * 2u : 0u);
@@ -3075,7 +3196,7 @@ __global__ __launch_bounds__(kBlock) void tcp_build_kernel(TcpHdrSoA h, const ui
                     const __amdgpu_buffer_rsrc_t ors = make_rsrc(out + readlane64(moo, kk), nb4);
                     u32x4 x = F.v[e][0];
                     if (OPT)  // image dwords [5, hdr/4): options and padding, not the source bytes under them
-                        x = staged_opts<true>(od, kk, (__builtin_amdgcn_readlane(mhdr, kk) - 20u) >> 2, lane, x);
+                        x = staged_opts<true, IPH>(od, kk, (__builtin_amdgcn_readlane(mhdr, kk) - 20u - IPH) >> 2, lane, x);
                     // header dwords broadcast from lane kk (pulling D0-D3 with ds_bpermute instead measured equal,
                     // DESIGN.md §7 step 46)
                     S.D0 = __builtin_amdgcn_readlane(mD0, kk);
@@ -3083,15 +3204,21 @@ __global__ __launch_bounds__(kBlock) void tcp_build_kernel(TcpHdrSoA h, const ui
                     S.D2 = __builtin_amdgcn_readlane(mD2, kk);
                     S.D3 = __builtin_amdgcn_readlane(mD3, kk);
                     S.D4 = __builtin_amdgcn_readlane(mD4, kk);
-                    x.x = lane == 0 ? S.D0 : (lane == 1 ? S.D4 : x.x);
-                    x.y = lane == 0 ? S.D1 : x.y;
-                    x.z = lane == 0 ? S.D2 : x.z;
-                    x.w = lane == 0 ? S.D3 : x.w;
+                    if constexpr (IPH == 0) {
+                        x.x = lane == 0 ? S.D0 : (lane == 1 ? S.D4 : x.x);
+                        x.y = lane == 0 ? S.D1 : x.y;
+                        x.z = lane == 0 ? S.D2 : x.z;
+                        x.w = lane == 0 ? S.D3 : x.w;
+                    } else {
+#pragma unroll
+                        for (int d = 0; d < kIpDw; ++d) S.I[d] = __builtin_amdgcn_readlane(mI[d], kk);
+                        put_headers<IPH, true>(x, S, lane);
+                    }
                     const u32x4 y = F.v[e][1];  // row 1: zeros past the image (range check), stores clipped likewise
                     const uint32_t raw = seg_raw(kk, fold32(sad4(y, sad4(x, 0u))));
                     // both rows leave once the sum is known, one store each: dword 4 (lane 1's first) carries the
                     // field (tcp.go:110, ^sum) — no separate partial-chunk or field stores
-                    x.x = lane == 1 ? S.D4 | bswap16u(~raw & 0xFFFFu) : x.x;
+                    set_comp(x, F::comp, S.D4 | bswap16u(~raw & 0xFFFFu), lane == F::lane);
                     __builtin_amdgcn_raw_buffer_store_b128(v4u{x.x, x.y, x.z, x.w}, ors, lane * 16u, 0, SP);
                     __builtin_amdgcn_raw_buffer_store_b128(v4u{y.x, y.y, y.z, y.w}, ors, kRow + lane * 16u, 0, SP);
                 }
@@ -3147,11 +3274,11 @@ __global__ __launch_bounds__(kBlock) void tcp_build_kernel(TcpHdrSoA h, const ui
                     __amdgpu_buffer_rsrc_t drs, ors;
                     seg_at(kk, S, drs, ors);
                     u32x4 oc0{0u, 0u, 0u, 0u};
-                    if (OPT && S.optlen) oc0 = staged_opts<false>(od, kk, (S.optlen + 3u) >> 2, lane, oc0);
-                    u32x4 x = compose_row(S, oc0, lane, 0, G.lo[e][0], G.hi[e][0]);
-                    const u32x4 y = compose_row(S, u32x4{0u, 0u, 0u, 0u}, lane, 1, G.lo[e][1], G.hi[e][1]);
+                    if (OPT && S.optlen) oc0 = staged_opts<false, IPH>(od, kk, (S.optlen + 3u) >> 2, lane, oc0);
+                    u32x4 x = compose_row<IPH>(S, oc0, lane, 0, G.lo[e][0], G.hi[e][0]);
+                    const u32x4 y = compose_row<IPH>(S, u32x4{0u, 0u, 0u, 0u}, lane, 1, G.lo[e][1], G.hi[e][1]);
                     const uint32_t raw = seg_raw(kk, fold32(sad4(y, sad4(x, 0u))));  // row 1 is 0 past the image
-                    x.x = lane == 1 ? S.D4 | bswap16u(~raw & 0xFFFFu) : x.x;  // the field, dword 4
+                    set_comp(x, F::comp, S.D4 | bswap16u(~raw & 0xFFFFu), lane == F::lane);  // the field, dword 4
                     __builtin_amdgcn_raw_buffer_store_b128(v4u{x.x, x.y, x.z, x.w}, ors, lane * 16u, 0, SP);
                     __builtin_amdgcn_raw_buffer_store_b128(v4u{y.x, y.y, y.z, y.w}, ors, kRow + lane * 16u, 0, SP);
                 }
@@ -3170,6 +3297,10 @@ __global__ __launch_bounds__(kBlock) void tcp_build_kernel(TcpHdrSoA h, const ui
         }
         uint32_t k = 0;
         while (k < cnt) {
+            if (IPH != 0 && __builtin_amdgcn_readlane(mskip, k)) {  // nothing written, raw sum 0
+                k += 1;
+                continue;
+            }
             BuildSeg S;
             __amdgpu_buffer_rsrc_t drs, ors;
             seg_at(k, S, drs, ors);
@@ -3186,7 +3317,7 @@ __global__ __launch_bounds__(kBlock) void tcp_build_kernel(TcpHdrSoA h, const ui
                 constexpr uint32_t R = kBuildRows;
                 const __amdgpu_buffer_rsrc_t frs = make_rsrc(data + S.db - S.hdr_end, S.nb4);
                 OptRaw o{};
-                if (S.optlen && !staged) o = opt_load(opts, S.ob, S.optlen, lane * 16u);
+                if (S.optlen && !staged) o = opt_load<IPH>(opts, S.ob, S.optlen, lane * 16u);
                 auto fl = [&](uint32_t r0, u32x4 (&v)[R]) {
 #pragma unroll
                     for (uint32_t rr = 0; rr < R; ++rr) v[rr] = bld16<LP != 0>(frs, (r0 + rr) * kRow + lane * 16u);
@@ -3201,23 +3332,23 @@ __global__ __launch_bounds__(kBlock) void tcp_build_kernel(TcpHdrSoA h, const ui
                         u32x4 x = v[rr];
                         if (r == 0) {
                             if (S.optlen && staged) {
-                                x = staged_opts<true>(od, k, (S.hdr_end - 20u) >> 2, lane, x);
+                                x = staged_opts<true, IPH>(od, k, (S.hdr_end - 20u - IPH) >> 2, lane, x);
                             } else if (S.optlen) {
-                                const u32x4 oc = opt_fin(o, S.ob, S.optlen, lane * 16u);
+                                const u32x4 oc = opt_fin<IPH>(o, S.ob, S.optlen, lane * 16u);
                                 x = keep_bytes(x, min(max((int32_t)S.hdr_end - (int32_t)(lane * 16u), 0), 16), 16);
                                 x.x |= oc.x, x.y |= oc.y, x.z |= oc.z, x.w |= oc.w;
                             }
-                            x.x = lane == 0 ? S.D0 : (lane == 1 ? S.D4 : x.x);
-                            x.y = lane == 0 ? S.D1 : x.y;
-                            x.z = lane == 0 ? S.D2 : x.z;
-                            x.w = lane == 0 ? S.D3 : x.w;
+                            if constexpr (IPH == 0) {
+                                x.x = lane == 0 ? S.D0 : (lane == 1 ? S.D4 : x.x);
+                                x.y = lane == 0 ? S.D1 : x.y;
+                                x.z = lane == 0 ? S.D2 : x.z;
+                                x.w = lane == 0 ? S.D3 : x.w;
+                            } else {
+                                put_headers<IPH, true>(x, S, lane);
+                            }
                         }
                         acc = sad4(x, acc);
-                        const uint32_t pos0 = r * kRow + lane * 16u;
-                        const bool d4 = r == 0 && lane == 1;  // dword 4 waits for the field
-                        __builtin_amdgcn_raw_buffer_store_b128(v4u{x.x, x.y, x.z, x.w}, ors, d4 ? kOOB : pos0, 0, SP);
-                        if (r == 0)
-                            __builtin_amdgcn_raw_buffer_store_b96(v3u{x.y, x.z, x.w}, ors, d4 ? 20u : kOOB, 0, SP);
+                        store_held<IPH, SP>(x, ors, lane, r, r * kRow + lane * 16u);  // dword 4 waits for the field
                     }
                     acc = fold32(acc);
                 };
@@ -3236,7 +3367,7 @@ __global__ __launch_bounds__(kBlock) void tcp_build_kernel(TcpHdrSoA h, const ui
                 u32x4 lo[R];
                 uint32_t hi[R];
                 OptRaw o{};
-                if (S.optlen && !staged) o = opt_load(opts, S.ob, S.optlen, lane * 16u);  // hdr_end ≤ 1008: row 0
+                if (S.optlen && !staged) o = opt_load<IPH>(opts, S.ob, S.optlen, lane * 16u);  // hdr_end ≤ 1008: row 0
                 build_load_head<LP>(drs, S, lane, lo[0], hi[0]);
 #pragma unroll
                 for (uint32_t rr = 1; rr < R; ++rr) build_load_body<LP>(drs, S, lane, rr, lo[rr], hi[rr]);
@@ -3244,12 +3375,12 @@ __global__ __launch_bounds__(kBlock) void tcp_build_kernel(TcpHdrSoA h, const ui
                 for (uint32_t rr = 0; rr < R; ++rr)
                     asm volatile("" : "+v"(lo[rr].x), "+v"(lo[rr].y), "+v"(lo[rr].z), "+v"(lo[rr].w), "+v"(hi[rr]));
                 const u32x4 oc0 = !S.optlen ? u32x4{0u, 0u, 0u, 0u}
-                                  : staged  ? staged_opts<false>(od, k, (S.optlen + 3u) >> 2, lane, u32x4{0u, 0u, 0u, 0u})
-                                            : opt_fin(o, S.ob, S.optlen, lane * 16u);
+                                  : staged  ? staged_opts<false, IPH>(od, k, (S.optlen + 3u) >> 2, lane, u32x4{0u, 0u, 0u, 0u})
+                                            : opt_fin<IPH>(o, S.ob, S.optlen, lane * 16u);
 #pragma unroll
                 for (uint32_t rr = 0; rr < R; ++rr)
                     if (rr < S.rows)
-                        acc = build_row<SP>(S, ors, rr == 0 ? oc0 : u32x4{0u, 0u, 0u, 0u}, lane, rr, lo[rr], hi[rr], acc);
+                        acc = build_row<SP, IPH>(S, ors, rr == 0 ? oc0 : u32x4{0u, 0u, 0u, 0u}, lane, rr, lo[rr], hi[rr], acc);
                 acc = fold32(acc);
                 for (uint32_t r0 = R; r0 < S.rows; r0 += R) {  // long segments: further batches
 #pragma unroll
@@ -3260,7 +3391,7 @@ __global__ __launch_bounds__(kBlock) void tcp_build_kernel(TcpHdrSoA h, const ui
 #pragma unroll
                     for (uint32_t rr = 0; rr < R; ++rr)
                         if (r0 + rr < S.rows)
-                            acc = build_row<SP>(S, ors, u32x4{0u, 0u, 0u, 0u}, lane, r0 + rr, lo[rr], hi[rr], acc);
+                            acc = build_row<SP, IPH>(S, ors, u32x4{0u, 0u, 0u, 0u}, lane, r0 + rr, lo[rr], hi[rr], acc);
                     acc = fold32(acc);
                 }
             } else {
@@ -3273,10 +3404,10 @@ __global__ __launch_bounds__(kBlock) void tcp_build_kernel(TcpHdrSoA h, const ui
                     for (int j = 0; j < 5; ++j)
                         d[j] = __builtin_amdgcn_raw_buffer_load_b32(drs, t + j >= 0 ? (uint32_t)(t + j) * 4u : kOOB, 0,
                                                                      2);
-                    const u32x4 oc = r * kRow < 20u + S.optlen ? opt_fin(opt_load(opts, S.ob, S.optlen, pos0), S.ob,
-                                                                         S.optlen, pos0)
-                                                               : u32x4{0u, 0u, 0u, 0u};
-                    acc = fold32(build_row<SP>(S, ors, oc, lane, r, u32x4{d[0], d[1], d[2], d[3]}, d[4], acc));
+                    const u32x4 oc = r * kRow < IPH + 20u + S.optlen
+                                         ? opt_fin<IPH>(opt_load<IPH>(opts, S.ob, S.optlen, pos0), S.ob, S.optlen, pos0)
+                                         : u32x4{0u, 0u, 0u, 0u};
+                    acc = fold32(build_row<SP, IPH>(S, ors, oc, lane, r, u32x4{d[0], d[1], d[2], d[3]}, d[4], acc));
                 }
             }
             seg_done(k, S, ors, acc);
@@ -4242,10 +4373,11 @@ hipError_t launch_verify_mask(const uint16_t* raw, uint64_t n, uint64_t* mask, u
 
 constexpr uint64_t kBuildGroupBytes = 24576;  // images per TCP build wave task, about
 
-hipError_t launch_tcp_build(const LaunchCfg& c, const TcpHdrSoA& h, const uint8_t* opts, const uint64_t* opt_off,
-                            const uint8_t* data, const uint64_t* data_off, uint64_t data_bytes,
-                            const uint32_t* partial, uint64_t n, uint8_t* out, const uint64_t* out_off,
-                            uint16_t* raw, hipStream_t st) {
+// ip: the transmit pass's IP fields (ipver 4 or 6); null = TCP images only (ipver ignored, partial as given)
+hipError_t launch_tcp_build(const LaunchCfg& c, int ipver, const IpHdrSoA* ip, const TcpHdrSoA& h,
+                            const uint8_t* opts, const uint64_t* opt_off, const uint8_t* data,
+                            const uint64_t* data_off, uint64_t data_bytes, const uint32_t* partial, uint64_t n,
+                            uint8_t* out, const uint64_t* out_off, uint16_t* raw, hipStream_t st) {
     // Path by layout: groups of ≤ 2-row images software-pipelined (the fast composition when every segment of
     // the group allows it, else the general one); longer images unpipelined. kernel 2 forces the unpipelined
     // path, kernel 3 the general pipelined composition (test coverage of those paths on every layout).
@@ -4258,7 +4390,7 @@ hipError_t launch_tcp_build(const LaunchCfg& c, const TcpHdrSoA& h, const uint8_
     // 0.946). The image size comes from the payload bytes per segment the caller passes.
     const uint32_t max_blocks = max_blocks_of(c, 2);
     const uint64_t waves = (uint64_t)max_blocks * kWavesPerBlock;
-    const uint64_t wire = data_bytes / n + 20;  // mean image bytes (options aside)
+    const uint64_t wire = data_bytes / n + 20 + (ip ? (ipver == 4 ? 20 : 40) : 0);  // mean image bytes (options aside)
     const uint64_t by_size = std::max<uint64_t>(1, (kBuildGroupBytes + wire / 2) / wire);
     uint32_t group = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(16, by_size), std::max<uint64_t>(1, (n + waves - 1) / waves));
     if (c.run_segs >= 1 && c.run_segs <= 64) group = (uint32_t)c.run_segs;
@@ -4266,12 +4398,23 @@ hipError_t launch_tcp_build(const LaunchCfg& c, const TcpHdrSoA& h, const uint8_
     const uint32_t grid = grid_for(tasks, max_blocks);
     const uint32_t clog = deal_clog(c.xcd_chunk, tasks, (uint64_t)group * 2u * wire);  // payload + image per segment
     const int pipe = c.kernel == 2 ? 0 : c.kernel == 3 ? 2 : 1;
+    if (ip) {
+#define NSX_TX_LAUNCH(IPH, OPT)                                                                                   \
+    hipLaunchKernelGGL((tcp_build_kernel<0, 0, 2, OPT, IPH>), dim3(grid), dim3(kBlock), 0, st, h, opts, opt_off,   \
+                       data, data_off, data_bytes, nullptr, n, out, out_off, raw, group, clog, pipe, IpArgs<IPH>{*ip})
+        if (ipver == 4 && opt_off) NSX_TX_LAUNCH(20, true);
+        else if (ipver == 4) NSX_TX_LAUNCH(20, false);
+        else if (opt_off) NSX_TX_LAUNCH(40, true);
+        else NSX_TX_LAUNCH(40, false);
+#undef NSX_TX_LAUNCH
+        return hipGetLastError();
+    }
     if (opt_off)
         hipLaunchKernelGGL((tcp_build_kernel<0, 0, 2, true>), dim3(grid), dim3(kBlock), 0, st, h, opts, opt_off, data,
-                           data_off, data_bytes, partial, n, out, out_off, raw, group, clog, pipe);
+                           data_off, data_bytes, partial, n, out, out_off, raw, group, clog, pipe, IpArgs<0>{});
     else
         hipLaunchKernelGGL((tcp_build_kernel<0, 0, 2, false>), dim3(grid), dim3(kBlock), 0, st, h, opts, opt_off, data,
-                           data_off, data_bytes, partial, n, out, out_off, raw, group, clog, pipe);
+                           data_off, data_bytes, partial, n, out, out_off, raw, group, clog, pipe, IpArgs<0>{});
     return hipGetLastError();
 }
 

@@ -361,7 +361,11 @@ int run_sharded(const uint8_t* h_base, uint64_t stride, uint32_t seg_len, const 
 // buffered over the shard's two streams like the checksum chunks above. The staged payload keeps its byte offset
 // mod 256 and sits ≥ 256 B into its buffer, and the image span keeps its offset mod 256, so every segment takes the
 // kernel path it would take in a device-resident batch at a 256-aligned base.
+// The transmit pass (nsx_tx_ipv4_tcp_build_host / nsx_tx_ipv6_tcp_build_host) is the same job with an IP part: its
+// six nsx_ip_hdr_soa arrays ride in the field block behind the TCP fields, and the kernel writes whole datagrams.
 struct BuildJob {
+    const nsx_ip_hdr_soa* ip;  // host arrays; null = TCP images only
+    int ipver;                 // 4 or 6 with ip
     const nsx_tcp_hdr_soa* h;  // host arrays
     const uint8_t* opts;
     const uint64_t* opt_off;  // nullable
@@ -380,9 +384,28 @@ struct BuildJob {
 
 constexpr uint64_t kFieldAlign = 256;
 
-uint64_t field_block_bytes(uint64_t cn) {  // 8 sub-arrays of cn entries, each 256 B-aligned
-    const uint64_t a = kFieldAlign - 1;
-    return 2 * ((2 * cn + a) & ~a) + 2 * ((4 * cn + a) & ~a) + 2 * ((2 * cn + a) & ~a) + 2 * ((cn + a) & ~a);
+constexpr int kTcpFields = 8, kIpFields = 6;
+
+// The job's field arrays (null where the caller passed none) and their entry sizes: 8 TCP, then 6 IP.
+int field_arrays(const BuildJob& j, const void* (&src)[kTcpFields + kIpFields], uint64_t (&esz)[kTcpFields + kIpFields]) {
+    const void* t[kTcpFields] = {j.h->src_port, j.h->dst_port,   j.h->seq_num, j.h->ack_num,
+                                 j.h->window,   j.h->urgent_ptr, j.h->offset,  j.h->control};
+    const uint64_t ts[kTcpFields] = {2, 2, 4, 4, 2, 2, 1, 1};
+    for (int f = 0; f < kTcpFields; ++f) src[f] = t[f], esz[f] = ts[f];
+    if (!j.ip) return kTcpFields;
+    const uint64_t alen = j.ipver == 4 ? 4 : 16;
+    const void* a[kIpFields] = {j.ip->src, j.ip->dst, j.ip->ident, j.ip->ttl, j.ip->tclass, j.ip->flow};
+    const uint64_t as[kIpFields] = {alen, alen, 2, 1, 1, 4};
+    for (int f = 0; f < kIpFields; ++f) src[kTcpFields + f] = a[f], esz[kTcpFields + f] = as[f];
+    return kTcpFields + kIpFields;
+}
+
+uint64_t field_block_bytes(const BuildJob& j, uint64_t cn) {  // sub-arrays of cn entries, each 256 B-aligned
+    const void* src[kTcpFields + kIpFields];
+    uint64_t esz[kTcpFields + kIpFields], at = 0;
+    const int nf = field_arrays(j, src, esz);
+    for (int f = 0; f < nf; ++f) at += (cn * esz[f] + kFieldAlign - 1) & ~(kFieldAlign - 1);
+    return at;
 }
 
 void run_build_job(BuildJob* j) {
@@ -431,8 +454,8 @@ void run_build_job(BuildJob* j) {
         if (!st[s]) NSX_TRY(hipStreamCreateWithFlags(&st[s], hipStreamNonBlocking));
         NSX_TRY(ctx->d_data[s].ensure(512 + max_data + 16));
         NSX_TRY(ctx->d_out[s].ensure(256 + max_out + 16));
-        NSX_TRY(ctx->d_fields[s].ensure(field_block_bytes(max_segs)));
-        NSX_TRY(ctx->h_fstage[s].ensure(field_block_bytes(max_segs)));
+        NSX_TRY(ctx->d_fields[s].ensure(field_block_bytes(*j, max_segs)));
+        NSX_TRY(ctx->h_fstage[s].ensure(field_block_bytes(*j, max_segs)));
         NSX_TRY(ctx->d_off[s].ensure(noffs * (max_segs + 1) * sizeof(uint64_t)));
         NSX_TRY(ctx->h_offstage[s].ensure(noffs * (max_segs + 1) * sizeof(uint64_t)));
         NSX_TRY(ctx->d_raw[s].ensure(std::max<uint64_t>(max_segs * sizeof(uint16_t), 16)));
@@ -459,15 +482,15 @@ void run_build_job(BuildJob* j) {
             NSX_TRY(hipStreamSynchronize(st[s]));
             finish(s);
         }
-        // header fields: 8 sub-arrays in one pinned block, one copy
+        // header fields: the sub-arrays in one pinned block, one copy
         uint8_t* hf = ctx->h_fstage[s].as<uint8_t>();
         uint8_t* df = ctx->d_fields[s].as<uint8_t>();
-        const void* src_f[8] = {j->h->src_port, j->h->dst_port, j->h->seq_num, j->h->ack_num,
-                                j->h->window,   j->h->urgent_ptr, j->h->offset, j->h->control};
-        const uint64_t esz[8] = {2, 2, 4, 4, 2, 2, 1, 1};
-        const void* dev_f[8];
+        const void* src_f[kTcpFields + kIpFields];
+        uint64_t esz[kTcpFields + kIpFields];
+        const int nf = field_arrays(*j, src_f, esz);
+        const void* dev_f[kTcpFields + kIpFields] = {};
         uint64_t at = 0;
-        for (int f = 0; f < 8; ++f) {
+        for (int f = 0; f < nf; ++f) {
             dev_f[f] = src_f[f] ? df + at : nullptr;
             if (src_f[f]) std::memcpy(hf + at, (const uint8_t*)src_f[f] + c.c0 * esz[f], cn * esz[f]);
             at += (cn * esz[f] + kFieldAlign - 1) & ~(kFieldAlign - 1);
@@ -516,9 +539,12 @@ void run_build_job(BuildJob* j) {
         const nsx::TcpHdrSoA h{(const uint16_t*)dev_f[0], (const uint16_t*)dev_f[1], (const uint32_t*)dev_f[2],
                                (const uint32_t*)dev_f[3], (const uint8_t*)dev_f[6],  (const uint8_t*)dev_f[7],
                                (const uint16_t*)dev_f[4], (const uint16_t*)dev_f[5]};
+        const nsx::IpHdrSoA ipd{(const uint8_t*)dev_f[8],  (const uint8_t*)dev_f[9],  (const uint16_t*)dev_f[10],
+                                (const uint8_t*)dev_f[11], (const uint8_t*)dev_f[12], (const uint32_t*)dev_f[13]};
         uint16_t* d_raw = ctx->d_raw[s].as<uint16_t>();
-        NSX_TRY(nsx::launch_tcp_build(cfg, h, d_opts, j->opt_off ? dofs + 2 * (cn + 1) : nullptr, d_data, dofs,
-                                      lead_d + span_d, d_part, cn, d_out, dofs + cn + 1, j->raw ? d_raw : nullptr, st[s]));
+        NSX_TRY(nsx::launch_tcp_build(cfg, j->ipver, j->ip ? &ipd : nullptr, h, d_opts,
+                                      j->opt_off ? dofs + 2 * (cn + 1) : nullptr, d_data, dofs, lead_d + span_d, d_part,
+                                      cn, d_out, dofs + cn + 1, j->raw ? d_raw : nullptr, st[s]));
         if (span_o) NSX_TRY(hipMemcpyAsync(out_dst, d_out + lead_o, span_o, hipMemcpyDeviceToHost, st[s]));
         if (j->raw)
             NSX_TRY(hipMemcpyAsync(ctx->h_rawstage[s].p, d_raw, cn * sizeof(uint16_t), hipMemcpyDeviceToHost, st[s]));
@@ -569,6 +595,36 @@ int run_build_sharded(const BuildJob& proto, uint64_t n, int num_gpus, const nsx
     for (const BuildJob& j : jobs)
         if (j.rc != NSX_OK) return j.rc;
     return NSX_OK;
+}
+
+// nsx_tcp_build_host (ip null) and the transmit pass's host calls (ip + ipver): validation, then the sharded job.
+int build_host(const nsx_ip_hdr_soa* ip, int ipver, const nsx_tcp_hdr_soa* h_hdr, const uint8_t* h_opts,
+               const uint64_t* h_opt_off, const uint8_t* h_data, const uint64_t* h_data_off,
+               const uint32_t* h_prefix_partial, uint64_t n, uint8_t* h_out, const uint64_t* h_out_off, uint16_t* h_raw,
+               int num_gpus, const nsx_tune* tune) {
+    if (n == 0) return NSX_OK;
+    if (!h_hdr || !h_hdr->src_port || !h_hdr->dst_port || !h_hdr->seq_num || !h_hdr->ack_num || !h_hdr->control ||
+        !h_hdr->window || !h_hdr->urgent_ptr || !h_data_off || !h_out || !h_out_off || (h_opt_off && !h_opts))
+        return NSX_EINVAL;
+    // every span the chunks copy must be well-formed: non-decreasing offsets, 4-aligned image slots that hold
+    // their image and its zero padding (nsx_tcp_build_dev's layout rule), images shorter than 2^31 bytes; a
+    // datagram's TCP part must fit the IP length field (the device call would leave such a frame unbuilt)
+    if (h_data_off[n] > h_data_off[0] && !h_data) return NSX_EINVAL;
+    const uint64_t iph = !ip ? 0 : ipver == 4 ? 20 : 40, wire_max = !ip ? ~0ull : ipver == 4 ? 65515 : 65535;
+    bool gaps = false;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (h_data_off[i + 1] < h_data_off[i] || (h_opt_off && h_opt_off[i + 1] < h_opt_off[i]) ||
+            h_out_off[i + 1] < h_out_off[i] || (h_out_off[i] & 3))
+            return NSX_EINVAL;
+        const uint64_t ol = h_opt_off ? h_opt_off[i + 1] - h_opt_off[i] : 0;
+        const uint64_t wire = nsx_tcp_wire_len(ol, h_data_off[i + 1] - h_data_off[i]);
+        const uint64_t slot = (iph + wire + 3) & ~3ull;
+        if (wire > wire_max || slot >= (1ull << 31) || h_out_off[i + 1] - h_out_off[i] < slot) return NSX_EINVAL;
+        gaps |= h_out_off[i + 1] - h_out_off[i] > slot;
+    }
+    const BuildJob proto{ip,   ipver, h_hdr, h_opts, h_opt_off, h_data, h_data_off, h_prefix_partial, h_out, h_out_off,
+                         h_raw, gaps, 0,     0,      0,         0,      tune,       NSX_OK};
+    return run_build_sharded(proto, n, num_gpus, tune);
 }
 
 }  // namespace
@@ -645,26 +701,42 @@ int nsx_tcp_build_host_tuned(const nsx_tcp_hdr_soa* h_hdr, const uint8_t* h_opts
                              const uint8_t* h_data, const uint64_t* h_data_off, const uint32_t* h_prefix_partial,
                              uint64_t n, uint8_t* h_out, const uint64_t* h_out_off, uint16_t* h_raw, int num_gpus,
                              const nsx_tune* tune) {
-    if (n == 0) return NSX_OK;
-    if (!h_hdr || !h_hdr->src_port || !h_hdr->dst_port || !h_hdr->seq_num || !h_hdr->ack_num || !h_hdr->control ||
-        !h_hdr->window || !h_hdr->urgent_ptr || !h_data_off || !h_out || !h_out_off || (h_opt_off && !h_opts))
-        return NSX_EINVAL;
-    // every span the chunks copy must be well-formed: non-decreasing offsets, 4-aligned image slots that hold
-    // their image and its zero padding (nsx_tcp_build_dev's layout rule), images shorter than 2^31 bytes
-    if (h_data_off[n] > h_data_off[0] && !h_data) return NSX_EINVAL;
-    bool gaps = false;
-    for (uint64_t i = 0; i < n; ++i) {
-        if (h_data_off[i + 1] < h_data_off[i] || (h_opt_off && h_opt_off[i + 1] < h_opt_off[i]) ||
-            h_out_off[i + 1] < h_out_off[i] || (h_out_off[i] & 3))
-            return NSX_EINVAL;
-        const uint64_t ol = h_opt_off ? h_opt_off[i + 1] - h_opt_off[i] : 0;
-        const uint64_t slot = (nsx_tcp_wire_len(ol, h_data_off[i + 1] - h_data_off[i]) + 3) & ~3ull;
-        if (slot >= (1ull << 31) || h_out_off[i + 1] - h_out_off[i] < slot) return NSX_EINVAL;
-        gaps |= h_out_off[i + 1] - h_out_off[i] > slot;
-    }
-    const BuildJob proto{h_hdr, h_opts, h_opt_off, h_data, h_data_off, h_prefix_partial, h_out, h_out_off, h_raw,
-                         gaps,  0,      0,         0,      0,          tune,             NSX_OK};
-    return run_build_sharded(proto, n, num_gpus, tune);
+    return build_host(nullptr, 0, h_hdr, h_opts, h_opt_off, h_data, h_data_off, h_prefix_partial, n, h_out, h_out_off,
+                      h_raw, num_gpus, tune);
+}
+
+int nsx_tx_ipv4_tcp_build_host(const nsx_ip_hdr_soa* h_ip, const nsx_tcp_hdr_soa* h_tcp, const uint8_t* h_opts,
+                               const uint64_t* h_opt_off, const uint8_t* h_data, const uint64_t* h_data_off,
+                               uint64_t n, uint8_t* h_out, const uint64_t* h_out_off, uint16_t* h_tcp_raw,
+                               int num_gpus) {
+    return nsx_tx_ipv4_tcp_build_host_tuned(h_ip, h_tcp, h_opts, h_opt_off, h_data, h_data_off, n, h_out, h_out_off,
+                                            h_tcp_raw, num_gpus, nullptr);
+}
+
+int nsx_tx_ipv4_tcp_build_host_tuned(const nsx_ip_hdr_soa* h_ip, const nsx_tcp_hdr_soa* h_tcp, const uint8_t* h_opts,
+                                     const uint64_t* h_opt_off, const uint8_t* h_data, const uint64_t* h_data_off,
+                                     uint64_t n, uint8_t* h_out, const uint64_t* h_out_off, uint16_t* h_tcp_raw,
+                                     int num_gpus, const nsx_tune* tune) {
+    if (n && (!h_ip || !h_ip->src || !h_ip->dst)) return NSX_EINVAL;
+    return build_host(h_ip, 4, h_tcp, h_opts, h_opt_off, h_data, h_data_off, nullptr, n, h_out, h_out_off, h_tcp_raw,
+                      num_gpus, tune);
+}
+
+int nsx_tx_ipv6_tcp_build_host(const nsx_ip_hdr_soa* h_ip, const nsx_tcp_hdr_soa* h_tcp, const uint8_t* h_opts,
+                               const uint64_t* h_opt_off, const uint8_t* h_data, const uint64_t* h_data_off,
+                               uint64_t n, uint8_t* h_out, const uint64_t* h_out_off, uint16_t* h_tcp_raw,
+                               int num_gpus) {
+    return nsx_tx_ipv6_tcp_build_host_tuned(h_ip, h_tcp, h_opts, h_opt_off, h_data, h_data_off, n, h_out, h_out_off,
+                                            h_tcp_raw, num_gpus, nullptr);
+}
+
+int nsx_tx_ipv6_tcp_build_host_tuned(const nsx_ip_hdr_soa* h_ip, const nsx_tcp_hdr_soa* h_tcp, const uint8_t* h_opts,
+                                     const uint64_t* h_opt_off, const uint8_t* h_data, const uint64_t* h_data_off,
+                                     uint64_t n, uint8_t* h_out, const uint64_t* h_out_off, uint16_t* h_tcp_raw,
+                                     int num_gpus, const nsx_tune* tune) {
+    if (n && (!h_ip || !h_ip->src || !h_ip->dst)) return NSX_EINVAL;
+    return build_host(h_ip, 6, h_tcp, h_opts, h_opt_off, h_data, h_data_off, nullptr, n, h_out, h_out_off, h_tcp_raw,
+                      num_gpus, tune);
 }
 
 int nsx_host_cache_release(void) {

@@ -108,11 +108,21 @@ def lib() -> ctypes.CDLL:
             "nsx_csum_ragged_host_tuned": [vp, vp, u64, vp, vp, i32, vp],
             "nsx_tcp_build_host": [vp, vp, vp, vp, vp, vp, u64, vp, vp, vp, i32],
             "nsx_tcp_build_host_tuned": [vp, vp, vp, vp, vp, vp, u64, vp, vp, vp, i32, vp],
+            "nsx_tx_layout_host": [vp, vp, u64, u32, vp],
+            "nsx_tx_ipv4_tcp_build_dev": [vp, vp, vp, vp, vp, vp, u64, u64, vp, vp, vp, vp],
+            "nsx_tx_ipv6_tcp_build_dev": [vp, vp, vp, vp, vp, vp, u64, u64, vp, vp, vp, vp],
+            "nsx_tx_ipv4_tcp_build_dev_tuned": [vp, vp, vp, vp, vp, vp, u64, u64, vp, vp, vp, vp, vp],
+            "nsx_tx_ipv6_tcp_build_dev_tuned": [vp, vp, vp, vp, vp, vp, u64, u64, vp, vp, vp, vp, vp],
+            "nsx_tx_ipv4_tcp_build_host": [vp, vp, vp, vp, vp, vp, u64, vp, vp, vp, i32],
+            "nsx_tx_ipv6_tcp_build_host": [vp, vp, vp, vp, vp, vp, u64, vp, vp, vp, i32],
+            "nsx_tx_ipv4_tcp_build_host_tuned": [vp, vp, vp, vp, vp, vp, u64, vp, vp, vp, i32, vp],
+            "nsx_tx_ipv6_tcp_build_host_tuned": [vp, vp, vp, vp, vp, vp, u64, vp, vp, vp, i32, vp],
             "nsx_fixed_launch_count": [u64, u32, u64, vp, ctypes.POINTER(u64)],
             "nsx_ipv4_hdr_launch_count": [vp, u64, u32, u64, vp, ctypes.POINTER(u64)],
         }
-        # present since ABI round 6; an older library (same-box A/B against a previous build) lacks them
-        optional = {"nsx_stream_release", "nsx_deal_sets_in_use"}
+        # present since ABI round 6, and the transmit pass since its own change; an older library (same-box A/B against a
+        # previous build) lacks them
+        optional = {"nsx_stream_release", "nsx_deal_sets_in_use"} | {k for k in sig if k.startswith("nsx_tx_")}
         for name, args in sig.items():
             if name in optional and not hasattr(L, name):
                 continue
@@ -581,6 +591,160 @@ def tcp_build_host(fields: dict, data: np.ndarray, data_off: np.ndarray, out_off
                                           _np_ptr(data_off), _np_ptr(part), n, _np_ptr(out), _np_ptr(out_off),
                                           _np_ptr(raw), num_gpus, _tune(tune)), "nsx_tcp_build_host")
     return out, raw
+
+
+# ---------------------------------------------------------------------------
+# fused transmit pass: whole IPv4 / IPv6 datagrams (nsx_tx_*)
+# ---------------------------------------------------------------------------
+IP_FIELDS = ("src", "dst", "ident", "ttl", "tclass", "flow")  # nsx_ip_hdr_soa members
+
+
+class IpHdrSoA(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name in IP_FIELDS]
+
+
+def _ip_sizes(ipver: int) -> dict:
+    """Bytes per frame of each nsx_ip_hdr_soa array."""
+    if ipver not in (4, 6):
+        raise ValueError(f"ipver must be 4 or 6, got {ipver}")
+    alen = 4 if ipver == 4 else 16
+    return {"src": alen, "dst": alen, "ident": 2, "ttl": 1, "tclass": 1, "flow": 4}
+
+
+def tx_layout_host(data_off: np.ndarray, opt_off: np.ndarray | None = None, ip_hdr_len: int = 20) -> np.ndarray:
+    """nsx_tx_layout_host: packed 4-aligned frame offsets, out_off[i] = Σ_{j<i} round_up4(ip_hdr_len + wire_j)
+    (ip_hdr_len 20 for IPv4, 40 for IPv6)."""
+    data_off = np.ascontiguousarray(data_off, np.uint64)
+    n = data_off.size - 1
+    out = np.zeros(n + 1, np.uint64)
+    oo = None if opt_off is None else np.ascontiguousarray(opt_off, np.uint64)
+    if oo is not None and oo.size < n + 1:
+        raise ValueError(f"tx_layout_host opt_off: {oo.size} entries for {n} frames")
+    _check(lib().nsx_tx_layout_host(_np_ptr(oo), _np_ptr(data_off), n, ip_hdr_len, _np_ptr(out)), "nsx_tx_layout_host")
+    return out
+
+
+def _tx_build_dev(ipver: int, ip: dict, fields: dict, data, data_off, out, out_off, opts, opt_off, raw, stream, tune):
+    what = f"tx_ipv{ipver}_tcp_build_dev"
+    n = _count(data_off, f"{what} data_off")
+    sizes = _ip_sizes(ipver)
+    for k in ("src", "dst"):
+        if ip.get(k) is None:
+            raise ValueError(f"{what}: address array {k!r} missing")
+    for k in IP_FIELDS:
+        _span(ip.get(k), sizes[k] * n, f"{what} {k}", elem=None if k in ("src", "dst") else sizes[k])
+    for k, size in BUILD_FIELDS:
+        if fields.get(k) is None and k != "offset":  # only byte 12 may be computed on the device
+            raise ValueError(f"{what}: header field {k!r} missing")
+        _span(fields.get(k), size * n, f"{what} {k}", elem=size)
+    _span(data, 0, f"{what} data")
+    _span(out_off, 8 * (n + 1), f"{what} out_off", elem=8)
+    # the frame lengths are in device memory; the least n frames can take is an IP and a TCP header each
+    _span(out, max(n, 0) * (40 if ipver == 4 else 60), f"{what} out", elem=1)
+    _span(opt_off, 8 * (n + 1), f"{what} opt_off", elem=8)
+    if opt_off is not None and opts is None:
+        raise ValueError(f"{what}: opt_off given without opts")
+    _span(opts, 0, f"{what} opts")
+    _span(raw, 2 * n, f"{what} raw", elem=2)
+    ipsoa = IpHdrSoA(*[_dev_ptr(ip.get(k)) for k in IP_FIELDS])
+    soa = TcpHdrSoA(*[_dev_ptr(fields.get(k)) for k, _ in BUILD_FIELDS])
+    fn = getattr(lib(), f"nsx_tx_ipv{ipver}_tcp_build_dev_tuned")
+    _check(fn(ctypes.byref(ipsoa), ctypes.byref(soa), _dev_ptr(opts), _dev_ptr(opt_off), _dev_ptr(data),
+              _dev_ptr(data_off), data.numel(), n, _dev_ptr(out), _dev_ptr(out_off), _dev_ptr(raw), _stream(stream),
+              _tune(tune)), f"nsx_{what}")
+    return out
+
+
+def tx_ipv4_tcp_build_dev(ip: dict, fields: dict, data, data_off, out, out_off, opts=None, opt_off=None, raw=None,
+                          stream=None, tune=None):
+    """Fused transmit pass: whole IPv4 datagrams (header checksum and TCP checksum in place) at out + out_off[i].
+    ip: dict of device tensors src, dst (uint8, 4 B per frame) and optionally ident (2 B), ttl (1 B); fields,
+    opts and the layout rule as tcp_build_dev; raw (optional) receives the TCP raw sums."""
+    return _tx_build_dev(4, ip, fields, data, data_off, out, out_off, opts, opt_off, raw, stream, tune)
+
+
+def tx_ipv6_tcp_build_dev(ip: dict, fields: dict, data, data_off, out, out_off, opts=None, opt_off=None, raw=None,
+                          stream=None, tune=None):
+    """The same for IPv6: src, dst 16 B per frame; optionally ttl (hop limit), tclass (1 B), flow (4 B)."""
+    return _tx_build_dev(6, ip, fields, data, data_off, out, out_off, opts, opt_off, raw, stream, tune)
+
+
+_IP_NP = {"src": np.uint8, "dst": np.uint8, "ident": np.uint16, "ttl": np.uint8, "tclass": np.uint8, "flow": np.uint32}
+
+
+def _tx_build_host(ipver: int, ip: dict, fields: dict, data, data_off, out_off, opts, opt_off, out, want_raw, num_gpus,
+                   tune):
+    what = f"tx_ipv{ipver}_tcp_build_host"
+    data = np.ascontiguousarray(data, np.uint8)
+    data_off = np.ascontiguousarray(data_off, np.uint64)
+    n = data_off.size - 1
+    sizes = _ip_sizes(ipver)
+    ipc = {}
+    for k in IP_FIELDS:
+        v = ip.get(k)
+        if v is None:
+            if k in ("src", "dst"):
+                raise ValueError(f"{what}: address array {k!r} missing")
+            continue
+        v = np.ascontiguousarray(v, _IP_NP[k])
+        if v.nbytes < sizes[k] * n:
+            raise ValueError(f"{what} {k}: {v.nbytes} B given, {sizes[k] * n} B needed")
+        ipc[k] = v
+    cols = {}
+    for k, _ in BUILD_FIELDS:
+        v = fields.get(k)
+        if v is None:
+            if k != "offset":
+                raise ValueError(f"{what}: header field {k!r} missing")
+            continue
+        v = np.ascontiguousarray(v, _BUILD_NP[k])
+        if v.size < n:
+            raise ValueError(f"{what} {k}: {v.size} entries for {n} frames")
+        cols[k] = v
+    oo = None if opt_off is None else np.ascontiguousarray(opt_off, np.uint64)
+    if oo is not None and opts is None:
+        raise ValueError(f"{what}: opt_off given without opts")
+    if oo is not None and oo.size < n + 1:
+        raise ValueError(f"{what} opt_off: {oo.size} entries for {n} frames")
+    ob = None if opts is None else (np.ascontiguousarray(opts, np.uint8) if len(opts) else np.zeros(1, np.uint8))
+    if out_off is None:
+        out_off = tx_layout_host(data_off, oo, 20 if ipver == 4 else 40)
+    out_off = np.ascontiguousarray(out_off, np.uint64)
+    if out_off.size < n + 1:
+        raise ValueError(f"{what} out_off: {out_off.size} entries for {n} frames")
+    if n > 0 and data.size < int(data_off[-1]):
+        raise ValueError(f"{what} data: {data.size} B given, data_off ends at {int(data_off[-1])}")
+    if oo is not None and n > 0 and ob.size < int(oo[-1]):
+        raise ValueError(f"{what} opts: {ob.size} B given, opt_off ends at {int(oo[-1])}")
+    if out is None:
+        out = np.zeros(int(out_off[-1]) if n > 0 else 0, np.uint8)
+    if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or not out.flags.c_contiguous:
+        raise ValueError(f"{what} out: needs a C-contiguous uint8 array")
+    if n > 0 and out.size < int(out_off[n]):
+        raise ValueError(f"{what} out: {out.size} B given, out_off ends at {int(out_off[n])}")
+    raw = np.empty(max(n, 0), np.uint16) if want_raw else None
+    ipsoa = IpHdrSoA(*[_np_ptr(ipc.get(k)) for k in IP_FIELDS])
+    soa = TcpHdrSoA(*[_np_ptr(cols.get(k)) for k, _ in BUILD_FIELDS])
+    fn = getattr(lib(), f"nsx_tx_ipv{ipver}_tcp_build_host_tuned")
+    _check(fn(ctypes.byref(ipsoa), ctypes.byref(soa), _np_ptr(ob), _np_ptr(oo), _np_ptr(data), _np_ptr(data_off), n,
+              _np_ptr(out), _np_ptr(out_off), _np_ptr(raw), num_gpus, _tune(tune)), f"nsx_{what}")
+    return out, raw
+
+
+def tx_ipv4_tcp_build_host(ip: dict, fields: dict, data: np.ndarray, data_off: np.ndarray,
+                           out_off: np.ndarray | None = None, opts: np.ndarray | None = None,
+                           opt_off: np.ndarray | None = None, out: np.ndarray | None = None, want_raw: bool = True,
+                           num_gpus: int = 0, tune=None):
+    """The fused transmit pass over host-resident inputs (nsx_tx_ipv4_tcp_build_host): ip and fields are dicts of
+    host arrays; out_off defaults to nsx_tx_layout_host. Returns (out, raw or None)."""
+    return _tx_build_host(4, ip, fields, data, data_off, out_off, opts, opt_off, out, want_raw, num_gpus, tune)
+
+
+def tx_ipv6_tcp_build_host(ip: dict, fields: dict, data: np.ndarray, data_off: np.ndarray,
+                           out_off: np.ndarray | None = None, opts: np.ndarray | None = None,
+                           opt_off: np.ndarray | None = None, out: np.ndarray | None = None, want_raw: bool = True,
+                           num_gpus: int = 0, tune=None):
+    return _tx_build_host(6, ip, fields, data, data_off, out_off, opts, opt_off, out, want_raw, num_gpus, tune)
 
 
 def fill_splitmix64_dev(buf, seed: int, byte_off: int = 0, stream=None):
