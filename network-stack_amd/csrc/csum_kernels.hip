@@ -247,96 +247,6 @@ constexpr uint32_t kDealHeads = NSX_DEAL_HEADS;
 constexpr uint32_t kDealStride = 16;
 constexpr uint32_t kDealSlots = 64;
 
-// ---- Work dealt through a block's LDS ring (round 6) ----
-// A batch's last units are dealt to the waves as they finish, without any streaming wave waiting on a ticket's round
-// trip: one dealer wave per block pulls tickets (device-scope atomics on the stream's heads, 1-3 µs each) for the
-// entries its block's streaming waves have claimed and posts them in an LDS ring; a streaming wave claims entries
-// ahead (an LDS atomic) and reads them from LDS when it gets there. vmcnt retires in issue order, so a ticket pulled
-// by a streaming wave itself would hold up every load issued after it (§7 step 72). The receive pass's streamed
-// modes (rx_runs_ring) and the fixed-stride kernel (csum_fixed_swp_kernel<·, ·, true>) use it.
-constexpr uint32_t kPieceRing = 64;        // ring entries per block
-constexpr uint32_t kPieceFree = ~0u;       // an entry read by its consumer (or never written)
-
-struct PieceRing {
-    uint32_t claim;     // entries claimed by the streaming waves (LDS atomic add)
-    uint32_t produced;  // entries the dealer has written, in order
-    uint32_t end_at;    // the dealer's final entry count once its head's share ran out (~0 until then)
-    uint32_t pad;
-    uint32_t e[kPieceRing];  // entry p at e[p % kPieceRing]: a piece's first frame; kPieceFree once read
-};
-
-// A streaming wave's side of the block's ring: claim an entry (an LDS atomic), read a claimed entry (waiting for the
-// dealer only if it has not posted it yet; `end` past the share) and free its slot for the dealer.
-struct RingClient {
-    PieceRing* rg;
-    uint32_t lane;
-    __device__ __forceinline__ uint32_t claim() const {
-        uint32_t v = 0u;
-        if (lane == 0u) v = __hip_atomic_fetch_add(&rg->claim, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        return __builtin_amdgcn_readfirstlane(v);
-    }
-    __device__ __forceinline__ uint32_t read(uint32_t idx, uint32_t end) const {  // entry idx's value, or end
-        for (;;) {
-            const uint32_t p = __builtin_amdgcn_readfirstlane(
-                __hip_atomic_load(&rg->produced, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
-            if (idx < p) {
-                uint32_t* slot = &rg->e[idx % kPieceRing];
-                const uint32_t v = __builtin_amdgcn_readfirstlane(
-                    __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-                if (lane == 0u) __hip_atomic_store(slot, kPieceFree, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                return v;
-            }
-            const uint32_t e = __builtin_amdgcn_readfirstlane(
-                __hip_atomic_load(&rg->end_at, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
-            if (idx >= e) return end;
-            __builtin_amdgcn_s_sleep(1);
-        }
-    }
-};
-
-// The dealer wave of a block: for every entry its streaming waves claim, a ticket t from the block's head (at most
-// 4 pulls in flight), posted to the ring as the piece's first unit pb + t·unit; past the head's share it posts the end. The head's dword 0 is the ticket
-// counter (shared with DealtRuns, which leaves it at 0), dword 1 counts the head's dealers that have finished: the
-// last one to finish resets both to 0 for the stream's next launch (a dealer may pull up to 4 tickets past the
-// share, so the pull count cannot mark the last pull as in DealtRuns).
-__device__ __forceinline__ void ring_dealer(PieceRing* rg, uint32_t* head, uint32_t pb, uint32_t unit, uint32_t qh,
-                                            uint32_t dealers, uint32_t ahead, uint32_t lane) {
-    uint32_t p = 0u;
-    bool live = true;
-    while (live) {
-        // entries to post: every claimed one, plus `ahead` more, up to 16 per round trip
-        const uint32_t c = __builtin_amdgcn_readfirstlane(
-            __hip_atomic_load(&rg->claim, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
-        const uint32_t k = min(c + ahead - p, 16u);
-        if (k == 0u || (int32_t)(c + ahead - p) <= 0) {
-            __builtin_amdgcn_s_sleep(2);
-            continue;
-        }
-        // k tickets in one pull: base .. base + k − 1, of which those below qh are the head's share
-        uint32_t t = 0u;
-        if (lane == 0u) t = __hip_atomic_fetch_add(head, k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint32_t base = __builtin_amdgcn_readfirstlane(t);
-        const uint32_t v = base < qh ? min(k, qh - base) : 0u;
-        // lane j < v posts entry p + j; its slot's previous entry must have been read (rarely waits)
-        uint32_t* slot = &rg->e[(p + lane) % kPieceRing];
-        while (__builtin_amdgcn_ballot_w64(lane < v && __hip_atomic_load(slot, __ATOMIC_RELAXED,
-                                                                        __HIP_MEMORY_SCOPE_WORKGROUP) != kPieceFree))
-            __builtin_amdgcn_s_sleep(1);
-        if (lane < v) __hip_atomic_store(slot, pb + (base + lane) * unit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        p += v;
-        live = v == k;
-        if (lane == 0u) __hip_atomic_store(&rg->produced, p, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-    if (lane == 0u) {
-        __hip_atomic_store(&rg->end_at, p, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        const uint32_t done = __hip_atomic_fetch_add(head + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (done + 1u == dealers) {
-            __hip_atomic_store(head, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(head + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-}
-
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, uint64_t bytes) {
     // Wave-uniform inputs only, so no waterfall loop (guide T20); clamp without a
     // 64-bit unsigned compare (SALU has none: hipcc would borrow VGPRs for it).
@@ -467,82 +377,17 @@ __global__ __launch_bounds__(kBlock) void csum_fixed_buf_kernel(
 // pipelined: two register sets of one task each (U segments × NROWS rows); the next task's loads are issued
 // before the current task is reduced, so a wave keeps its loads in flight through its own reduce/park/flush
 // phases instead of leaving them to other waves.
-//
-// DEAL (round 6): the batch's last 1/2^kDealPoolShift of the tasks are not split statically
-// but dealt through the block's LDS ring (ring_dealer) to the four streaming waves as they finish: a fifth wave per
-// block pulls the tickets from the stream's heads. With equal static shares the launch waited ~12 µs (5%) for its
-// last waves — the XCDs and CUs run at different speeds (tools/probes/f3_wave_times.py --config 2,
-// profiles/r06_fixed_wave_times_c2.txt). A dealt task's 8 results are finished with their own partials and stored
-// at once (16 B).
-#ifndef NSX_FIXED_AHEAD
-#define NSX_FIXED_AHEAD 4
-#endif
-constexpr uint32_t kFixedAhead = NSX_FIXED_AHEAD;  // ring entries the dealer posts beyond the claimed ones
-#ifndef NSX_FIXED_POOL_SHIFT
-#define NSX_FIXED_POOL_SHIFT 3
-#endif
-constexpr uint32_t kFixedPoolShift = NSX_FIXED_POOL_SHIFT;  // the dealt pool: the last 1/2^k of the tasks
-#ifndef NSX_FIXED_DEAL_MODE
-#define NSX_FIXED_DEAL_MODE 0
-#endif
-constexpr int kFixedDealMode = NSX_FIXED_DEAL_MODE;  // the aligned default shapes' deal: 0 none, 1 dealer wave, 2 in-wave
-// DEAL 1: the dealer wave and ring above; DEAL 2: each wave pulls its own tickets from the heads, two tasks ahead
-// (two ticket registers alternating with the two register sets, so no ticket is ever copied or selected — reading one
-// waits only for its own pull, issued two task-loads earlier; round 6 A/B).
-template <int U, int NROWS, int DEAL = 0>
-__global__ __launch_bounds__(DEAL == 1 ? kBlock + kWave : kBlock) void csum_fixed_swp_kernel(
+template <int U, int NROWS>
+__global__ __launch_bounds__(kBlock) void csum_fixed_swp_kernel(
     const uint8_t* __restrict__ base, uint64_t stride, uint32_t seg_len, uint32_t n,
-    const uint32_t* __restrict__ partial, uint16_t* __restrict__ out, uint32_t chunk_log2,
-    uint32_t* __restrict__ deal) {
+    const uint32_t* __restrict__ partial, uint16_t* __restrict__ out, uint32_t chunk_log2) {
     constexpr uint32_t G = kWave / U;
     const uint32_t lane = threadIdx.x & (kWave - 1);
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     WaveStamps ws;
     ws.entry();
     uint32_t ntk = 0;  // tasks done (for the stamps)
-    const uint32_t all_tasks = (n + U - 1) / U;
-    uint32_t ntasks = all_tasks;  // the statically split tasks [0, ntasks)
-    [[maybe_unused]] RingClient rc{nullptr, lane};
-    [[maybe_unused]] uint32_t claim0 = 0, claim1 = 0;
-    // DEAL 2: this wave's head (waves numbered XCD by XCD: every head has waves on all 8 XCDs), its share of the
-    // pool, and the two tickets pulled at entry (held through the static part)
-    [[maybe_unused]] uint32_t* shead = nullptr;
-    [[maybe_unused]] uint32_t spb = 0, sq = 0, swaves = 0, tkx = 0, tky = 0;
-    auto spull = [&]() {
-        uint32_t t = 0u;
-        if (lane == 0u) t = __hip_atomic_fetch_add(shead, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return t;
-    };
-    if constexpr (DEAL == 2) {
-        ntasks = all_tasks - (all_tasks >> kFixedPoolShift);
-        const uint32_t W = gridDim.x * kWavesPerBlock, H = min(kDealHeads, W);
-        const uint32_t h = wave_number(gridDim.x, kWavesPerBlock, wave) % H;
-        const uint32_t Q = all_tasks - ntasks;
-        const uint32_t r0 = (uint32_t)((uint64_t)Q * h / H);
-        sq = (uint32_t)((uint64_t)Q * (h + 1u) / H) - r0;
-        spb = ntasks + r0;
-        swaves = (W - h + H - 1u) / H;
-        shead = deal + h * kDealStride;
-    }
-    if constexpr (DEAL == 1) {
-        __shared__ PieceRing ring;
-        ntasks = all_tasks - (all_tasks >> kFixedPoolShift);
-        if (wave == kWavesPerBlock) {
-            if (lane < kPieceRing) ring.e[lane] = kPieceFree;
-            if (lane == 0u) ring.claim = 0u, ring.produced = 0u, ring.end_at = ~0u;
-        }
-        __syncthreads();
-        if (wave == kWavesPerBlock) {  // the dealer: head h (blocks numbered XCD by XCD), its share of the pool
-            const uint32_t nb = gridDim.x, H = min(kDealHeads, nb), h = wave_number(nb, 1u, 0u) % H;
-            const uint32_t Q = all_tasks - ntasks;
-            const uint32_t r0 = (uint32_t)((uint64_t)Q * h / H), qh = (uint32_t)((uint64_t)Q * (h + 1u) / H) - r0;
-            ring_dealer(&ring, deal + h * kDealStride, ntasks + r0, 1u, qh, (nb - h + H - 1u) / H, kFixedAhead, lane);
-            return;
-        }
-        rc.rg = &ring;
-        claim0 = rc.claim();  // two pool entries claimed ahead from the start: posted by the time they are needed
-        claim1 = rc.claim();
-    }
+    const uint32_t ntasks = (n + U - 1) / U;
     TaskIter it = task_iter(ntasks, wave);
     const ChunkDeal cd = chunk_deal(it, wave, chunk_log2, ntasks);
     const uint32_t end = (uint32_t)it.end, step = (uint32_t)it.step;
@@ -597,138 +442,19 @@ __global__ __launch_bounds__(DEAL == 1 ? kBlock + kWave : kBlock) void csum_fixe
     };
     Set A, B;
     uint32_t i = (uint32_t)it.next;
-    // DEAL 2: the two first tickets are pulled when the static stream has at most two tasks left, so that they are
-    // in hand when the pool starts and the waves' pulls spread over their different end times (pulled at entry, the
-    // 2048 pulls of a launch queued on 32 counters at once)
-    [[maybe_unused]] bool pulled = false;
-    auto pull_late = [&](uint32_t inext) {
-        if constexpr (DEAL == 2) {
-            if (!pulled && !(inext < end && cd.task(inext) < ntasks)) {
-                tkx = spull();
-                tky = spull();
-                pulled = true;
-            }
-        }
-    };
     issue(i, A);
     while (A.ok) {
         const uint32_t i1 = i + step;
-        pull_late(i1 + step);
         issue(i1, B);
         consume(i, A);
         if (!B.ok) break;
         i = i1 + step;
-        pull_late(i + step);
         issue(i, A);
         consume(i1, B);
-    }
-    if constexpr (DEAL == 2) {
-        if (!pulled) tkx = spull(), tky = spull();
     }
     if (k) {
         res = finish(res, true, gpart);
         fixed_flush<U>(res, first, step, k, n, ors, lane, cd);
-    }
-    if constexpr (DEAL != 0) {
-        // The pool: tasks read from the ring (each claimed two tasks ahead), software-pipelined like the static
-        // loop; a task's partials load with its rows, its results are finished and stored when it is summed.
-        struct PSet {
-            u32x4 v[U][NROWS];
-            uint32_t t, part;
-        };
-        auto take = [&]() {
-            const uint32_t t = rc.read(claim0, all_tasks);
-            claim0 = claim1;
-            if (t < all_tasks) claim1 = rc.claim();
-            return t;
-        };
-        auto pissue = [&](uint32_t t, PSet& S) {
-            S.t = t;
-            const bool ok = t < all_tasks;
-            const uint32_t s0 = (ok ? t : 0u) * U;
-            const uint8_t* p = base + (uint64_t)s0 * stride;
-#pragma unroll
-            for (int u = 0; u < U; ++u, p += stride) {
-                const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(
-                    const_cast<uint8_t*>(p), 0, (ok && s0 + u < n) ? (int)seg_len : 0, 0x00020000);
-#pragma unroll
-                for (int rr = 0; rr < NROWS; ++rr) S.v[u][rr] = bld16<true>(r, rr * kRow + lane * 16);
-            }
-            S.part = __builtin_amdgcn_raw_buffer_load_b32(prs, ok && lane < (uint32_t)U && s0 + lane < n ? (s0 + lane) * 4
-                                                                                                          : kOOB, 0, 0);
-        };
-        auto pconsume = [&](PSet& S) {
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int rr = 0; rr < NROWS; ++rr) asm volatile("" : "+v"(S.v[u][rr]));
-            uint32_t r = 0;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                uint32_t acc = 0;
-#pragma unroll
-                for (int rr = 0; rr < NROWS; ++rr) acc = sad4(S.v[u][rr], acc);
-                const uint32_t tot = wave_sum(fold32(acc));
-                r = lane == (uint32_t)u ? tot : r;
-            }
-            r = finish(r, true, S.part);
-            const uint32_t seg = S.t * U + lane;
-            __builtin_amdgcn_raw_buffer_store_b16((uint16_t)r, ors, lane < (uint32_t)U && seg < n ? seg * 2 : kOOB, 0, 0);
-            ++ntk;
-        };
-        PSet P0, P1;
-        if constexpr (DEAL == 1) {
-            pissue(take(), P0);
-            while (P0.t < all_tasks) {
-                pissue(take(), P1);
-                pconsume(P0);
-                if (P1.t >= all_tasks) break;
-                pissue(take(), P0);
-                pconsume(P1);
-            }
-        } else {
-            // ticket register X feeds set P0, Y feeds P1; each is read two task-loads after its pull and refilled at
-            // once while the share lasts. A wave stops at the first ticket past the share and then reads its other
-            // outstanding pull too (a ticket is never dropped, whatever order the pulls executed in); the last wave of
-            // the head to finish resets it (dword 0) and the finished count (dword 1) for the stream's next launch.
-            auto tk_task = [&](uint32_t v) { return v < sq ? spb + v : all_tasks; };
-            P1.t = all_tasks;
-            uint32_t tx = tk_task(__builtin_amdgcn_readfirstlane(tkx));
-            if (tx < all_tasks) tkx = spull();
-            pissue(tx, P0);
-            bool ymore = true;  // Y holds an unread pull
-            while (P0.t < all_tasks) {
-                const uint32_t ty = tk_task(__builtin_amdgcn_readfirstlane(tky));
-                ymore = false;
-                if (ty < all_tasks) tky = spull(), ymore = true;
-                pissue(ty, P1);
-                pconsume(P0);
-                if (P1.t >= all_tasks) break;
-                tx = tk_task(__builtin_amdgcn_readfirstlane(tkx));
-                if (tx < all_tasks) tkx = spull();
-                pissue(tx, P0);
-                pconsume(P1);
-            }
-            // drain: P0 or P1 ended the loop with the end marker; the other ticket register may hold an unread pull
-            // (X if the loop ended on P1, else Y) — a valid one is a task to do
-            uint32_t last = all_tasks;
-            if (P1.t >= all_tasks && P0.t < all_tasks) {  // ended on P1: X was refilled when P0 was issued
-                last = tk_task(__builtin_amdgcn_readfirstlane(tkx));
-            } else if (ymore) {
-                last = tk_task(__builtin_amdgcn_readfirstlane(tky));
-            }
-            if (last < all_tasks) {  // rare: a pull executed out of order and returned inside the share; every pull
-                pissue(last, P0);    // after the one already seen past it returns past it too (one counter)
-                pconsume(P0);
-            }
-            if (lane == 0u) {
-                const uint32_t done = __hip_atomic_fetch_add(shead + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (done + 1u == swaves) {
-                    __hip_atomic_store(shead, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(shead + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-        }
     }
     ws.done(blockIdx.x * kWavesPerBlock + wave, ntk, lane);
 }
@@ -2237,94 +1963,6 @@ __device__ __forceinline__ void rx_runs(const uint8_t* __restrict__ base, __amdg
     }
 }
 
-// ---- The streamed modes' tail, dealt through the block's LDS (round 6) ----
-// With equal static shares the streamed receive pass (workloads 10, 11, 14: 12 waves per CU, ~5 runs of 64 frames
-// each, ~20 µs a run) waited 9-16 µs for its last waves — whole blocks run 3-4 µs apart (the waves of one block end
-// within ~1 µs of each other, profiles/r05_rx_wave_times_streamed.txt) — and dealing whole runs from the per-stream
-// heads (DealtRuns) would leave a tail of up to a run. Here the batch's last 1/2^kStreamPoolShift of frames is dealt
-// in pieces of kStreamPiece frames (~12 KB, ~5 µs), and the ticket round trip (a device-scope atomic, 1-3 µs) is
-// kept off the streaming waves altogether: each block runs three streaming waves and one dealer wave (4 blocks × 3
-// streaming waves per CU = the 12 of the static layout). The dealer pulls tickets from the stream's heads for the
-// pieces its waves have claimed and posts them in an LDS ring; a streaming wave claims its next piece one unit ahead
-// (an LDS atomic) and reads it from the ring when it moves on, so no vector-memory wait of a streaming wave ever
-// covers a ticket (vmcnt retires in issue order: loads issued behind an atomic wait for it too, §7 step 72).
-#ifndef NSX_STREAM_PIECE
-#define NSX_STREAM_PIECE 16
-#endif
-#ifndef NSX_STREAM_POOL_SHIFT
-#define NSX_STREAM_POOL_SHIFT 3
-#endif
-constexpr uint32_t kStreamPiece = NSX_STREAM_PIECE;          // frames per dealt piece (a multiple of 8: whole mask bytes)
-constexpr uint32_t kStreamPoolShift = NSX_STREAM_POOL_SHIFT;  // the pool: the batch's last eighth of frames
-constexpr uint32_t kStreamWaves = 3;       // streaming waves per block (wave 3 deals)
-#ifndef NSX_STREAM_AHEAD
-#define NSX_STREAM_AHEAD 0
-#endif
-constexpr uint32_t kStreamAhead = NSX_STREAM_AHEAD;  // entries the dealer posts beyond the claimed ones
-#ifndef NSX_STREAM_ROTATE
-#define NSX_STREAM_ROTATE 0
-#endif
-constexpr bool kStreamRotate = NSX_STREAM_ROTATE;
-#ifndef NSX_STREAM_DEAL
-#define NSX_STREAM_DEAL 0
-#endif
-constexpr bool kStreamDeal = NSX_STREAM_DEAL;  // the dealt streamed layout (A/B builds; the default: slot shares)
-
-// A streaming wave's units: its static runs [a0, e_st) of kRxRun frames, then dealt pieces until the share ends
-// (n). The entry for the unit after next is claimed when next() hands out a unit whose successor is a piece, and
-// read when next() moves on to it.
-struct RingRuns {
-    uint32_t a0, e_st, n;
-    RingClient rc;
-    uint32_t pend;  // the claimed entry not yet read (kPieceFree: none)
-    __device__ __forceinline__ uint32_t claim() const { return rc.claim(); }
-    __device__ __forceinline__ uint32_t read(uint32_t idx) const { return rc.read(idx, n); }
-    // after handing out unit r: is its successor a piece? then claim that piece's entry now
-    __device__ __forceinline__ uint32_t ahead(uint32_t r) {
-        if (r < n && (r >= e_st || r + kRxRun >= e_st)) pend = claim();
-        return r;
-    }
-    __device__ __forceinline__ uint32_t first() {
-        if (a0 < e_st) return ahead(a0);
-        return ahead(read(claim()));
-    }
-    __device__ __forceinline__ uint32_t next(uint32_t a) {
-        uint32_t r;
-        if (a + kRxRun < e_st) {
-            r = a + kRxRun;
-        } else {
-            r = pend == kPieceFree ? n : read(pend);
-            pend = kPieceFree;
-        }
-        return ahead(r);
-    }
-    __device__ __forceinline__ uint32_t cnt(uint32_t a) const {
-        return a < e_st ? min(kRxRun, e_st - a) : min(kStreamPiece, n - a);
-    }
-};
-
-// A streaming wave's units (RingRuns) in the streaming form, the offsets of the next unit loaded one unit ahead.
-template <int R, bool V6>
-__device__ __forceinline__ void rx_runs_ring(const uint8_t* __restrict__ base, __amdgpu_buffer_rsrc_t ofs, uint32_t n,
-                                             RingRuns& q, uint32_t lane, const RxOuts& ro) {
-    typedef uint32_t v2u __attribute__((ext_vector_type(2)));
-    auto load_off = [&](uint32_t i, bool live) -> uint64_t {
-        const v2u x = __builtin_amdgcn_raw_buffer_load_b64(ofs, live ? i * 8 : kOOB, 0, 0);
-        return ((uint64_t)x.y << 32) | x.x;
-    };
-    uint32_t a = q.first();
-    uint64_t no = load_off(a + lane, a < n && a + lane <= n), ne = load_off(a + lane + 1, a < n && a + lane + 1 <= n);
-    while (a < n) {
-        uint32_t cnt[1] = {q.cnt(a)};
-        uint64_t my_off[1] = {no}, my_end[1] = {ne};
-        const uint32_t an = q.next(a);
-        no = load_off(an + lane, an < n && an + lane <= n);
-        ne = load_off(an + lane + 1, an < n && an + lane + 1 <= n);
-        rx_run_stream<R, V6, 1>(base, a, cnt, my_off, my_end, 0u, n, lane, ro);
-        a = an;
-    }
-}
-
 // The LDS form of the receive pass, for waves of small frames. A run of 64 frames whose
 // bytes fit kRxSlotRows rows is staged whole into the wave's LDS slot — coalesced 16 B-per-lane row loads, issued
 // one run ahead (the next run's rows are in flight while this one is summed), then ds_write_b128 — and each lane
@@ -2700,50 +2338,8 @@ __global__ __launch_bounds__(kBlock, WPS) void rx_tcp_kernel(const uint8_t* __re
                 else rx_runs_pfx<R, V6, 7, true>(base, ofs, n, q, lane, slot, ro);
             }
             ws.done(g, wr.bytes, lane);
-        } else if (kStreamDeal && deal && (sets == 0 || sets == 8)) {
-            // Streamed runs with the batch's last eighth dealt in pieces through the block's LDS ring (the auto
-            // choice and mode 8 when the stream has heads; §7 step 75): waves 0-2 of every block stream, wave 3 deals.
-            // the dealer: wave 3, or (NSX_STREAM_ROTATE builds) the wave of the block's slot on its CU, so that the 4
-            // blocks of a CU put their dealers on different SIMDs
-            const uint32_t dw = kStreamRotate ? (uint32_t)((uint64_t)blockIdx.x * kWavesPerBlock / gridDim.x) : kStreamWaves;
-            PieceRing* rg = reinterpret_cast<PieceRing*>(lds_rx + dw * (PfxSlot<7>::kBytes / 16u));
-            static_assert(sizeof(PieceRing) <= PfxSlot<7>::kBytes && kPieceRing <= kWave, "the ring in the dealer's slot");
-            if (wave == dw) {
-                if (lane < kPieceRing) rg->e[lane] = kPieceFree;
-                if (lane == 0u) rg->claim = 0u, rg->produced = 0u, rg->end_at = ~0u;
-            }
-            __syncthreads();
-            const uint32_t nb = gridDim.x;
-            const uint32_t S = (n - (n >> kStreamPoolShift)) & ~(kRxRun - 1u);  // the static shares: frames [0, S)
-            if (wave == dw) {
-                // head h of the block (numbered XCD by XCD, so every head has blocks on all 8 XCDs), its share of the
-                // pool's pieces and its dealers
-                const uint32_t H = min(kDealHeads, nb), h = wave_number(nb, 1u, 0u) % H;
-                const uint32_t Q = (n - S + kStreamPiece - 1u) / kStreamPiece;
-                const uint32_t r0 = (uint32_t)((uint64_t)Q * h / H), qh = (uint32_t)((uint64_t)Q * (h + 1u) / H) - r0;
-                ring_dealer(rg, deal + h * kDealStride, S + r0 * kStreamPiece, kStreamPiece, qh, (nb - h + H - 1u) / H,
-                            kStreamAhead, lane);
-                return;
-            }
-            const uint32_t g = wave_number(nb, kStreamWaves, wave < dw ? wave : wave - 1u);
-            WaveRange wr{0u, 0u, 0u};
-            if (S > 0u) wr = wave_range(ofs, S, g, nb * kStreamWaves, lane, kRxSmallFrame, 8u);
-            RxOuts rp = ro;
-            if (ro.raw) {  // parked in the wave's 7-row slot, as below
-                uint16_t* pb = reinterpret_cast<uint16_t*>(lds_rx + wave * (PfxSlot<7>::kBytes / 16u));
-                rp.tpk = make_park<uint16_t>(pb, ro.trs, tcp_raw, wr.a0, V6 ? 4096u : 2048u);
-                if constexpr (!V6) rp.ipk = make_park<uint16_t>(pb + 2048, ro.irs, ip_raw, wr.a0, 2048u);
-            }
-            ws.ready();
-            RingRuns q{wr.a0, wr.a_end, n, RingClient{rg, lane}, kPieceFree};
-            rx_runs_ring<R, V6>(base, ofs, n, q, lane, rp);
-            if (ro.raw) {
-                park_flush(rp.tpk, lane);
-                if constexpr (!V6) park_flush(rp.ipk, lane);
-            }
-            ws.done(g, wr.bytes, lane);
-        } else {  // streamed runs on 3 of the 4 blocks per CU (the auto choice and mode 8, which forces it, on a
-                  // stream without heads); mode 1: on every block
+        } else {  // streamed runs on 3 of the 4 blocks per CU (the auto choice and mode 8, which forces it);
+                  // mode 1: on every block
             const uint32_t nb = active_blocks(ofs, n, 0u, sets == 0 || sets == 8 ? 3u : 0u);
             if (blockIdx.x >= nb) return;
             // byte shares weighted by the block's slot on its CU (slot_share) on the default grid: 4 blocks per CU
@@ -4011,8 +3607,6 @@ uint64_t fixed_launch_count(const LaunchCfg& c, uintptr_t /*base*/, uint64_t str
 }
 
 // One launch of the short-segment fixed path: U segments per wave task, NR rows per segment.
-static uint32_t* deal_heads(const LaunchCfg& c, hipStream_t st);  // below: the stream's work-deal counters
-
 static hipError_t launch_fixed_short(const LaunchCfg& c, const uint8_t* base, uint64_t stride, uint32_t seg_len,
                                      uint64_t n, const uint32_t* partial, uint16_t* out, int nrows, bool aligned,
                                      hipStream_t st) {
@@ -4025,26 +3619,11 @@ static hipError_t launch_fixed_short(const LaunchCfg& c, const uint8_t* base, ui
     const uint64_t ntasks = (n + u - 1) / u;
     const uint32_t grid = grid_for(ntasks, max_blocks_of(c, aligned ? 1 : 2));
     const uint32_t clog = deal_clog(c.xcd_chunk, ntasks, (uint64_t)u * stride);
-    // The default aligned shapes deal their last tasks through each block's ring (a fifth, dealer wave per block;
-    // §7 step 77) when the stream has heads and the batch has at least 64 tasks per block.
-    if (kFixedDealMode != 0 && aligned && c.segs_per_wave == 0 && ntasks >= 64ull * grid) {
-        if (uint32_t* deal = deal_heads(c, st)) {
-#define NSX_FIXED_DEAL(U_, NR_)                                                                                  \
-    if (u == U_ && nrows == NR_) {                                                                               \
-        hipLaunchKernelGGL((csum_fixed_swp_kernel<U_, NR_, kFixedDealMode>), dim3(grid),                          \
-                           dim3(kFixedDealMode == 1 ? kBlock + kWave : kBlock), 0, st, base, stride, seg_len,     \
-                           (uint32_t)n, partial, out, clog, deal);                                               \
-        return hipGetLastError();                                                                                \
-    }
-            NSX_FIXED_DEAL(8, 1) NSX_FIXED_DEAL(8, 2) NSX_FIXED_DEAL(4, 4)
-#undef NSX_FIXED_DEAL
-        }
-    }
 #define NSX_FIXED(U_, NR_)                                                                                    \
     if (u == U_ && nrows == NR_) {                                                                             \
         if (aligned)                                                                                           \
-            hipLaunchKernelGGL((csum_fixed_swp_kernel<U_, NR_, 0>), dim3(grid), dim3(kBlock), 0, st, base, stride, \
-                               seg_len, (uint32_t)n, partial, out, clog, nullptr);                             \
+            hipLaunchKernelGGL((csum_fixed_swp_kernel<U_, NR_>), dim3(grid), dim3(kBlock), 0, st, base, stride, \
+                               seg_len, (uint32_t)n, partial, out, clog);                                      \
         else                                                                                                   \
             hipLaunchKernelGGL((csum_fixed_buf_kernel<U_, NR_>), dim3(grid), dim3(kBlock), 0, st, base, stride, \
                                seg_len, (uint32_t)n, partial, out, clog);                                      \

@@ -147,12 +147,12 @@ def test_ragged_small_segment_bench_workload_full_size():
 
 
 def test_fixed_dealt_tasks_back_to_back_and_on_many_streams():
-    """The aligned fixed-stride kernel deals its last eighth of tasks through each block's LDS ring (a fifth, dealer
-    wave per block pulling from the stream's heads): the three default shapes (8 segments × 1
-    row, 8 × 2, 4 × 4), batch sizes from just over the dealing threshold (64 tasks per block) to 1M segments, with
-    and without partials, outputs 2 B past a 16 B boundary, launched back to back on one stream with no sync between
-    them — interleaved with the static split (deal -1) and with receive-pass launches that deal from the same heads —
-    then on 70 streams at once; every raw sum equals the oracle."""
+    """The aligned fixed-stride kernel splits its tasks statically on every launch (the dealt forms of DESIGN.md §7
+    step 77 were measured and deleted; the test keeps the name it had with them): the three default shapes (8
+    segments × 1 row, 8 × 2, 4 × 4), batch sizes from just under and over 64 tasks per block to 1M segments, with and
+    without partials, outputs 2 B past a 16 B boundary, launched back to back on one stream with no sync between them
+    — with and without deal -1, which this kernel ignores — interleaved with receive-pass launches that do deal from
+    the stream's heads — then on 70 streams at once; every raw sum and every receive mask equals the oracle."""
     import ctypes
     import _rx
     rng = np.random.default_rng(0x8D)

@@ -318,12 +318,13 @@ def test_rx_dealt_runs_back_to_back_and_on_many_streams():
 
 
 def test_rx_streamed_dealt_pieces_back_to_back_and_on_many_streams():
-    """The streamed modes deal the batch's last eighth in 16-frame pieces through each block's LDS ring: waves 0-2
-    stream, wave 3 pulls tickets from the stream's heads for the pieces they claim, and the last dealer of a head
-    resets it. IPv4 and IPv6 batches of 1 to 250k frames of full-size payloads (the streamed
-    choice), launched back to back on one stream with no sync between them — auto, forced mode 8, the static split
-    (deal -1) — interleaved with small-frame launches (mode 5, DealtRuns on the same heads), raw outputs 2 B past a
-    16 B boundary; then on 70 streams at once; every mask bit and raw sum equals the oracle."""
+    """The streamed modes run the static slot-share layout (byte shares weighted by the block's slot on its CU, §7 step
+    78; the dealt layout of step 75 was measured and deleted, the test keeps the name it had with it) next to the
+    two-wave DealtRuns modes, which deal from the stream's heads. IPv4 and IPv6 batches of 1 to 250k frames of
+    full-size payloads (the streamed choice), launched back to back on one stream with no sync between them — auto,
+    forced mode 8, deal -1 — interleaved with small-frame launches (mode 5, and a 40 B batch on auto: DealtRuns on the
+    stream's heads), raw outputs 2 B past a 16 B boundary; then on 70 streams at once; every mask bit and raw sum
+    equals the oracle."""
     import ctypes
     rng = np.random.default_rng(0x8C)
     cases = []
