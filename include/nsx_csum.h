@@ -245,6 +245,70 @@ int nsx_tx_ipv6_tcp_build_dev(const nsx_ip_hdr_soa* ip, const nsx_tcp_hdr_soa* t
 int nsx_tx_layout_host(const uint64_t* h_opt_off, const uint64_t* h_data_off, uint64_t n, uint32_t ip_hdr_len,
                        uint64_t* h_out_off);
 
+/* TCP segmentation offload on the fused transmit pass: the caller hands over n
+ * super-segments — per connection one header template, one option block and a
+ * run of payload far longer than one MSS — instead of one array entry per
+ * frame, and the transmit kernel cuts them. Super-segment s has one entry in
+ * every nsx_tcp_hdr_soa and nsx_ip_hdr_soa array, option bytes
+ * d_opts[d_opt_off[s], d_opt_off[s+1]), payload d_data[d_data_off[s],
+ * d_data_off[s+1]) of len_s bytes, and d_mss[s] >= 1, the payload bytes per
+ * frame (Linux gso_size: options and headers are not counted). It yields
+ * cnt_s = max(1, ceil(len_s / mss_s)) frames. Frame j of s (0 <= j < cnt_s) is
+ * exactly the frame nsx_tx_ipv4_tcp_build_dev / nsx_tx_ipv6_tcp_build_dev builds
+ * from s's fields, except:
+ *   payload   d_data[d_data_off[s] + j*mss, min(d_data_off[s] + (j+1)*mss,
+ *             d_data_off[s+1])) — empty when len_s == 0. The kernel reads no
+ *             payload byte outside s's own range, whatever the frame map says.
+ *   seq_num   seq_num[s] + j*mss modulo 2^32.
+ *   control   FIN (0x01) and PSH (0x08) are kept only on the last frame
+ *             (j == cnt_s - 1), CWR (0x80) only on the first (j == 0); every
+ *             other bit is copied to every frame. This is the rule of Linux's
+ *             tcp_gso_segment. SYN is merely copied: a caller does not offload
+ *             SYN segments.
+ *   ident     IPv4: (ident[s] + j) modulo 2^16, ident[s] = 0 when the array is
+ *             NULL. IPv6 flow label and traffic class are copied.
+ * Everything else — ack, window, urgent pointer, the options with the
+ * reference's padding, ports, addresses, TTL — is copied to every frame; with
+ * `offset` NULL, computeOffset() runs as in nsx_tcp_build_dev. The IPv4 total
+ * length / IPv6 payload length, the IPv4 header checksum, the pseudo-header and
+ * the TCP checksum follow from the frame's own slice. A frame whose TCP part
+ * does not fit its IP length field is not built and its raw sum is 0, as in
+ * the transmit pass.
+ * Frame map (host helpers below; the device calls take them as device arrays):
+ *   frame_first (n + 1): prefix sum of cnt_s — super-segment s owns frames
+ *     [frame_first[s], frame_first[s+1]); frame_first[n] = n_frames.
+ *   frame_seg (n_frames): the super-segment of each frame.
+ *   out_off (n_frames + 1): the frame slots, layout rule as the transmit pass.
+ * nsx_tso_count_host writes h_frame_first (NSX_EINVAL: a NULL array, an mss of
+ * 0, decreasing data offsets, n >= 2^32). nsx_tso_layout_host writes
+ * h_frame_seg and the packed offsets nsx_tx_layout_host would give the expanded
+ * batch, h_out_off[f] = sum of round_up4(ip_hdr_len + wire) over the frames
+ * before f (NSX_EINVAL as above, for decreasing option offsets, ip_hdr_len other
+ * than 20 or 40, and an h_frame_first that is not nsx_tso_count_host's).
+ * h_opt_off is nullable in both the layout and the build calls.
+ * d_tcp_raw (nullable) has n_frames entries. The device calls validate their
+ * pointers as the transmit pass does, return NSX_OK without a launch when
+ * n_frames == 0, and do no allocation, no host sync and use no per-stream
+ * counters: they can be captured into a graph. data_bytes = the extent of
+ * d_data, as in nsx_tcp_build_dev.
+ * There is no segmenting form of the IP-less nsx_tcp_build_dev: its caller-made
+ * pseudo-header partial depends on each frame's own length, so it cannot be
+ * given once per super-segment. */
+int nsx_tso_count_host(const uint64_t* h_data_off, const uint32_t* h_mss, uint64_t n, uint64_t* h_frame_first);
+int nsx_tso_layout_host(const uint64_t* h_opt_off, const uint64_t* h_data_off, const uint32_t* h_mss,
+                        const uint64_t* h_frame_first, uint64_t n, uint32_t ip_hdr_len, uint32_t* h_frame_seg,
+                        uint64_t* h_out_off);
+int nsx_tso_ipv4_tcp_build_dev(const nsx_ip_hdr_soa* ip, const nsx_tcp_hdr_soa* tcp, const uint8_t* d_opts,
+                               const uint64_t* d_opt_off, const uint8_t* d_data, const uint64_t* d_data_off,
+                               uint64_t data_bytes, const uint32_t* d_mss, uint64_t n,
+                               const uint64_t* d_frame_first, const uint32_t* d_frame_seg, uint64_t n_frames,
+                               uint8_t* d_out, const uint64_t* d_out_off, uint16_t* d_tcp_raw, nsx_stream_t stream);
+int nsx_tso_ipv6_tcp_build_dev(const nsx_ip_hdr_soa* ip, const nsx_tcp_hdr_soa* tcp, const uint8_t* d_opts,
+                               const uint64_t* d_opt_off, const uint8_t* d_data, const uint64_t* d_data_off,
+                               uint64_t data_bytes, const uint32_t* d_mss, uint64_t n,
+                               const uint64_t* d_frame_first, const uint32_t* d_frame_seg, uint64_t n_frames,
+                               uint8_t* d_out, const uint64_t* d_out_off, uint16_t* d_tcp_raw, nsx_stream_t stream);
+
 /* IPv4 header checksums (RFC 791 §3.1; SURVEY.md §8 f3 — the reference has no
  * IPv4 header codec, network/ip/v4/ipv4.go holds addresses only). Packet i's
  * header starts at d_base + i*stride + hdr_off (any alignment) and is IHL*4
@@ -375,6 +439,29 @@ int nsx_tx_ipv6_tcp_build_host(const nsx_ip_hdr_soa* h_ip, const nsx_tcp_hdr_soa
                                const uint64_t* h_opt_off, const uint8_t* h_data, const uint64_t* h_data_off,
                                uint64_t n, uint8_t* h_out, const uint64_t* h_out_off, uint16_t* h_tcp_raw,
                                int num_gpus);
+
+/* Segmentation offload (nsx_tso_ipv4_tcp_build_dev / nsx_tso_ipv6_tcp_build_dev)
+ * over host-resident inputs: the nsx_tx_*_build_host job with every array but
+ * h_out_off, h_frame_seg and h_tcp_raw (nullable, n_frames entries) holding one
+ * entry per super-segment. Checked before any copy (NSX_EINVAL): the offsets and
+ * h_mss as nsx_tso_count_host checks them, h_frame_first and h_frame_seg against
+ * what nsx_tso_count_host / nsx_tso_layout_host give, the frame slots against
+ * the layout rule, and every frame against its IP length field. Sharded by
+ * image bytes, chunks of <= 64 MiB double-buffered; a shard and a chunk end on
+ * a super-segment boundary, and a super-segment larger than the budget is a
+ * chunk of its own. A super-segment's fields, options and payload go to the
+ * device once, not once per frame; the frame map and the offsets are rebased
+ * per chunk. Pageable or pinned memory. */
+int nsx_tso_ipv4_tcp_build_host(const nsx_ip_hdr_soa* h_ip, const nsx_tcp_hdr_soa* h_tcp, const uint8_t* h_opts,
+                                const uint64_t* h_opt_off, const uint8_t* h_data, const uint64_t* h_data_off,
+                                const uint32_t* h_mss, uint64_t n, const uint64_t* h_frame_first,
+                                const uint32_t* h_frame_seg, uint64_t n_frames, uint8_t* h_out,
+                                const uint64_t* h_out_off, uint16_t* h_tcp_raw, int num_gpus);
+int nsx_tso_ipv6_tcp_build_host(const nsx_ip_hdr_soa* h_ip, const nsx_tcp_hdr_soa* h_tcp, const uint8_t* h_opts,
+                                const uint64_t* h_opt_off, const uint8_t* h_data, const uint64_t* h_data_off,
+                                const uint32_t* h_mss, uint64_t n, const uint64_t* h_frame_first,
+                                const uint32_t* h_frame_seg, uint64_t n_frames, uint8_t* h_out,
+                                const uint64_t* h_out_off, uint16_t* h_tcp_raw, int num_gpus);
 
 /* The host batch calls keep per-device streams and grow-only device/pinned
  * staging buffers across calls (a transport calls them once per batch). This

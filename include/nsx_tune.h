@@ -76,7 +76,11 @@ typedef struct nsx_tune {
                                   eighth dealt to the waves from the stream's counters where the stream allows
                                   it (nsx_csum.h, nsx_rx_ipv4_tcp_verify_dev), -1 = equal static shares
                                   throughout (A/B; replaces round 5's NSX_NO_DEAL build) */
-    int32_t reserved[5];
+    int32_t chunk_bytes;       /* the sender-side host calls (nsx_tcp_build_host, nsx_tx_*_build_host,
+                                  nsx_tso_*_build_host): bytes of images, and of payload, per double-buffered
+                                  chunk; 0 = 64 MiB. A segment (or super-segment) larger than this is a chunk
+                                  of its own. Tests reach the multi-chunk path with small batches */
+    int32_t reserved[4];
 } nsx_tune;
 
 int nsx_csum_fixed_dev_tuned(const void* d_base, uint64_t stride, uint32_t seg_len, uint64_t n,

@@ -381,6 +381,95 @@ int nsx_tx_ipv6_tcp_build_dev_tuned(const nsx_ip_hdr_soa* ip, const nsx_tcp_hdr_
                         stream, tune);
 }
 
+// ---- segmentation offload: the frame map on the host, then the transmit pass's launcher over super-segments ----
+// Frames of super-segment i: max(1, ceil(len / mss)).
+static uint64_t tso_frames(uint64_t len, uint32_t mss) { return len ? (len + mss - 1) / mss : 1; }
+
+int nsx_tso_count_host(const uint64_t* h_data_off, const uint32_t* h_mss, uint64_t n, uint64_t* h_frame_first) {
+    if (!h_frame_first || n >= (1ull << 32) || (n && (!h_data_off || !h_mss))) return NSX_EINVAL;
+    uint64_t at = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (h_mss[i] == 0 || h_data_off[i + 1] < h_data_off[i]) return NSX_EINVAL;
+        h_frame_first[i] = at;
+        at += tso_frames(h_data_off[i + 1] - h_data_off[i], h_mss[i]);
+    }
+    h_frame_first[n] = at;
+    return NSX_OK;
+}
+
+int nsx_tso_layout_host(const uint64_t* h_opt_off, const uint64_t* h_data_off, const uint32_t* h_mss,
+                        const uint64_t* h_frame_first, uint64_t n, uint32_t ip_hdr_len, uint32_t* h_frame_seg,
+                        uint64_t* h_out_off) {
+    if ((ip_hdr_len != 20 && ip_hdr_len != 40) || !h_out_off || !h_frame_first || n >= (1ull << 32) ||
+        (n && (!h_data_off || !h_mss)))
+        return NSX_EINVAL;
+    uint64_t f = 0;
+    for (uint64_t i = 0; i < n; ++i) {  // everything checked before anything is written
+        if (h_mss[i] == 0 || h_data_off[i + 1] < h_data_off[i] || (h_opt_off && h_opt_off[i + 1] < h_opt_off[i]) ||
+            h_frame_first[i] != f)
+            return NSX_EINVAL;
+        f += tso_frames(h_data_off[i + 1] - h_data_off[i], h_mss[i]);
+    }
+    if (h_frame_first[n] != f || (f && !h_frame_seg)) return NSX_EINVAL;
+    uint64_t at = 0;
+    f = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t ol = h_opt_off ? h_opt_off[i + 1] - h_opt_off[i] : 0;
+        const uint64_t len = h_data_off[i + 1] - h_data_off[i], cnt = tso_frames(len, h_mss[i]);
+        for (uint64_t j = 0; j < cnt; ++j, ++f) {
+            const uint64_t dl = std::min<uint64_t>(h_mss[i], len - j * h_mss[i]);
+            h_frame_seg[f] = (uint32_t)i;
+            h_out_off[f] = at;
+            at += (ip_hdr_len + nsx_tcp_wire_len(ol, dl) + 3) & ~3ull;
+        }
+    }
+    h_out_off[f] = at;
+    return NSX_OK;
+}
+
+static int tso_build_dev(int ipver, const nsx_ip_hdr_soa* ip, const nsx_tcp_hdr_soa* hdr, const uint8_t* d_opts,
+                         const uint64_t* d_opt_off, const uint8_t* d_data, const uint64_t* d_data_off,
+                         uint64_t data_bytes, const uint32_t* d_mss, uint64_t n, const uint64_t* d_frame_first,
+                         const uint32_t* d_frame_seg, uint64_t n_frames, uint8_t* d_out, const uint64_t* d_out_off,
+                         uint16_t* d_tcp_raw, nsx_stream_t stream, const nsx_tune* tune) {
+    if (n_frames == 0) return NSX_OK;
+    if (n == 0 || n >= (1ull << 32) || n_frames < n || !ip || !ip->src || !ip->dst || !hdr || !hdr->src_port ||
+        !hdr->dst_port || !hdr->seq_num || !hdr->ack_num || !hdr->control || !hdr->window || !hdr->urgent_ptr ||
+        !d_data_off || !d_mss || !d_frame_first || !d_frame_seg || !d_out || !d_out_off || (d_opt_off && !d_opts) ||
+        (data_bytes && !d_data))
+        return NSX_EINVAL;
+    const int dev = current_device();
+    if (dev < 0) return NSX_ENODEV;
+    const nsx::IpHdrSoA a{ip->src, ip->dst, ip->ident, ip->ttl, ip->tclass, ip->flow};
+    const nsx::TsoMap m{d_mss, d_frame_first, d_frame_seg};
+    const nsx::TcpHdrSoA h{hdr->src_port, hdr->dst_port, hdr->seq_num, hdr->ack_num,
+                           hdr->offset,   hdr->control,  hdr->window,  hdr->urgent_ptr};
+    return map_err(nsx::launch_tso_build(make_cfg(dev, tune), ipver, a, m, h, d_opts, d_opt_off, d_data, d_data_off,
+                                         data_bytes, n_frames, d_out, d_out_off, d_tcp_raw,
+                                         static_cast<hipStream_t>(stream)));
+}
+
+#define NSX_TSO_DEV(V)                                                                                              \
+    int nsx_tso_ipv##V##_tcp_build_dev(                                                                             \
+        const nsx_ip_hdr_soa* ip, const nsx_tcp_hdr_soa* tcp, const uint8_t* d_opts, const uint64_t* d_opt_off,     \
+        const uint8_t* d_data, const uint64_t* d_data_off, uint64_t data_bytes, const uint32_t* d_mss, uint64_t n,  \
+        const uint64_t* d_frame_first, const uint32_t* d_frame_seg, uint64_t n_frames, uint8_t* d_out,              \
+        const uint64_t* d_out_off, uint16_t* d_tcp_raw, nsx_stream_t stream) {                                      \
+        return tso_build_dev(V, ip, tcp, d_opts, d_opt_off, d_data, d_data_off, data_bytes, d_mss, n, d_frame_first, \
+                             d_frame_seg, n_frames, d_out, d_out_off, d_tcp_raw, stream, nullptr);                  \
+    }                                                                                                               \
+    int nsx_tso_ipv##V##_tcp_build_dev_tuned(                                                                       \
+        const nsx_ip_hdr_soa* ip, const nsx_tcp_hdr_soa* tcp, const uint8_t* d_opts, const uint64_t* d_opt_off,     \
+        const uint8_t* d_data, const uint64_t* d_data_off, uint64_t data_bytes, const uint32_t* d_mss, uint64_t n,  \
+        const uint64_t* d_frame_first, const uint32_t* d_frame_seg, uint64_t n_frames, uint8_t* d_out,              \
+        const uint64_t* d_out_off, uint16_t* d_tcp_raw, nsx_stream_t stream, const nsx_tune* tune) {                \
+        return tso_build_dev(V, ip, tcp, d_opts, d_opt_off, d_data, d_data_off, data_bytes, d_mss, n, d_frame_first, \
+                             d_frame_seg, n_frames, d_out, d_out_off, d_tcp_raw, stream, tune);                     \
+    }
+NSX_TSO_DEV(4)
+NSX_TSO_DEV(6)
+#undef NSX_TSO_DEV
+
 int nsx_tcp_parse_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n, const nsx_tcp_parsed_soa* out,
                       nsx_stream_t stream) {
     if (n == 0) return NSX_OK;

@@ -74,6 +74,18 @@ hipError_t launch_tcp_build(const LaunchCfg& c, int ipver, const IpHdrSoA* ip, c
                             const uint8_t* opts, const uint64_t* opt_off, const uint8_t* data,
                             const uint64_t* data_off, uint64_t data_bytes, const uint32_t* partial, uint64_t n,
                             uint8_t* out, const uint64_t* out_off, uint16_t* raw, hipStream_t st);
+// Segmentation offload (nsx_tso_*): the frame map over per-super-segment arrays (include/nsx_csum.h).
+struct TsoMap {
+    const uint32_t* mss;          // per super-segment: payload bytes per frame
+    const uint64_t* frame_first;  // per super-segment: its first frame
+    const uint32_t* frame_seg;    // per frame: its super-segment
+};
+// The transmit pass over super-segments: h, ip, opt_off and data_off hold one entry per super-segment; out_off
+// (n_frames + 1) and raw (n_frames, nullable) one per frame.
+hipError_t launch_tso_build(const LaunchCfg& c, int ipver, const IpHdrSoA& ip, const TsoMap& tso, const TcpHdrSoA& h,
+                            const uint8_t* opts, const uint64_t* opt_off, const uint8_t* data,
+                            const uint64_t* data_off, uint64_t data_bytes, uint64_t n_frames, uint8_t* out,
+                            const uint64_t* out_off, uint16_t* raw, hipStream_t st);
 struct TcpParsedSoA {  // device arrays, one entry per segment; every member nullable
     uint16_t* src_port;
     uint16_t* dst_port;

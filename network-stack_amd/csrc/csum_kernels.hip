@@ -2615,12 +2615,29 @@ __device__ __forceinline__ uint32_t build_row(const BuildSeg& S, __amdgpu_buffer
 // header's: 6 − (version/class/flow words) − (next header, hop limit word), in one's complement. The raw sum
 // is nonzero either way (the byte 6), so it is the same representative the serial loop reaches. No partials
 // array is read (`partial` is null). IPH 0 compiles to the TCP build unchanged (`ip` is empty).
-template <int IPH>
+//
+// TSO: segmentation offload (nsx_tso_ipv4_tcp_build_dev / nsx_tso_ipv6_tcp_build_dev). The field, option and
+// data_off arrays hold one entry per super-segment; n, out_off and raw_out count frames. Only the metadata phase
+// differs: lane k of a group loads frame g0+k's super-segment s = frame_seg[f] and its index j = f -
+// frame_first[s] in it, gathers s's fields (the lanes of one super-segment read the same addresses) and derives
+// its own slice [db + j·mss, min(db + (j+1)·mss, de)) of s's payload — clamped to s's range whatever the frame
+// map says — sequence number seq + j·mss, control byte (FIN and PSH on the last frame only, CWR on the first
+// only: Linux tcp_gso_segment's rule) and IPv4 ident + j. Everything downstream — lengths, the IPv4 header
+// checksum, the pseudo-header partial, the path choice, the staged options (lanes of one super-segment repeat
+// its option range: mob is non-decreasing over the group, so [gb, ge) still covers every lane's) — follows
+// from those per-lane values as it does for per-frame arrays. TSO false compiles to the per-frame pass unchanged.
+template <int IPH, bool TSO = false>
 struct IpArgs : IpHdrSoA {};
 template <>
-struct IpArgs<0> {};  // the TCP build takes no IP fields: an empty trailing argument
+struct IpArgs<0, false> {};  // the TCP build takes no IP fields: an empty trailing argument
+template <int IPH>
+struct IpArgs<IPH, true> : IpHdrSoA {
+    const uint32_t* mss;          // per super-segment: payload bytes per frame (≥ 1)
+    const uint64_t* frame_first;  // per super-segment: its first frame (prefix sum of the frame counts)
+    const uint32_t* frame_seg;    // per frame: its super-segment
+};
 
-template <int LP, int SP, int PS, bool OPT, int IPH = 0>
+template <int LP, int SP, int PS, bool OPT, int IPH = 0, bool TSO = false>
 __global__ __launch_bounds__(kBlock) void tcp_build_kernel(TcpHdrSoA h, const uint8_t* __restrict__ opts,
                                                            const uint64_t* __restrict__ opt_off,
                                                            const uint8_t* __restrict__ data,
@@ -2629,8 +2646,9 @@ __global__ __launch_bounds__(kBlock) void tcp_build_kernel(TcpHdrSoA h, const ui
                                                            uint8_t* __restrict__ out,
                                                            const uint64_t* __restrict__ out_off,
                                                            uint16_t* __restrict__ raw_out, uint32_t group,
-                                                           uint32_t clog, int pipe, IpArgs<IPH> ip) {
+                                                           uint32_t clog, int pipe, IpArgs<IPH, TSO> ip) {
     static_assert(IPH == 0 || IPH == 20 || IPH == 40, "TCP images, IPv4 or IPv6 datagrams");
+    static_assert(!TSO || IPH != 0, "segmentation needs the frame's own pseudo-header: transmit pass only");
     typedef uint32_t v4u __attribute__((ext_vector_type(4)));
     constexpr int kIpDw = IPH / 4;
     using F = FieldAt<IPH>;
@@ -2640,22 +2658,57 @@ __global__ __launch_bounds__(kBlock) void tcp_build_kernel(TcpHdrSoA h, const ui
     const uint64_t ngroups = (n + group - 1) / group;
     TaskIter it = task_iter(ngroups, wave);
     const ChunkDeal cd = chunk_deal(it, wave, clog, ngroups);
+    // TSO: a frame's fields hang off its super-segment index, one memory round trip behind the frame map. The
+    // wave loads that index a task ahead — the next task's with this task's fields — so that each task's metadata
+    // costs one round trip, as it does with per-frame arrays (3-frame jumbo tasks ran 3.1% slower without,
+    // DESIGN.md §7).
+    // (generic in the map, so that it is instantiated with the TSO arguments only)
+    [[maybe_unused]] auto tso_peek = [&](uint64_t q, const auto& m) -> uint32_t {  // the lane's frame_seg entry in task q
+        if (q >= it.end) return 0u;
+        const uint64_t g = cd.clog ? cd.task((uint32_t)q) : q;
+        if (g >= ngroups) return 0u;
+        const uint64_t g0 = g * group;
+        return m.frame_seg[g0 + min(lane, (uint32_t)min((uint64_t)group, n - g0) - 1u)];
+    };
+    [[maybe_unused]] uint32_t tnext = 0;
+    if constexpr (TSO) tnext = tso_peek(it.next, ip);
     for (uint64_t q = it.next; q < it.end; q += it.step) {
         const uint64_t g = cd.clog ? cd.task((uint32_t)q) : q;
         if (g >= ngroups) break;
         const uint64_t g0 = g * group;
         const uint32_t cnt = (uint32_t)min((uint64_t)group, n - g0);
         // Per-lane metadata of segment g0 + lane (lanes past cnt repeat the last one).
-        const uint64_t i = g0 + min(lane, cnt - 1);
+        const uint64_t fr = g0 + min(lane, cnt - 1);  // the lane's frame: its output slot
+        uint64_t i = fr;                              // its entry in the field, option and data_off arrays
+        uint32_t tj = 0, tmss = 0;                    // TSO: the frame's index in its super-segment; its mss
+        if constexpr (TSO) {
+            // the peeked entry has landed by now; taking it through a register constraint here keeps the loop-
+            // carried load out of the compiler's wait counting, which otherwise waits for the next peek at once
+            asm volatile("" : "+v"(tnext));
+            i = tnext;
+            tnext = tso_peek(q + it.step, ip);
+            tj = (uint32_t)(fr - ip.frame_first[i]);
+            tmss = ip.mss[i];
+        }
         const uint32_t mD0 = bswap16u(h.src_port[i]) | (bswap16u(h.dst_port[i]) << 16);
-        const uint32_t mD1 = bswap32u(h.seq[i]), mD2 = bswap32u(h.ack[i]);
+        uint32_t mD1 = bswap32u(h.seq[i]);
+        const uint32_t mD2 = bswap32u(h.ack[i]);
         const uint64_t mob = OPT ? opt_off[i] : 0;
         const uint32_t moptlen = OPT ? (uint32_t)(opt_off[i + 1] - mob) : 0u;
         // byte 12: the caller's, or computeOffset() (tcp.go:59-66) over the serialized option bytes
         const uint32_t moff = h.offset ? (uint32_t)h.offset[i] : ((23u + moptlen) >> 2) & 0xFFu;
-        const uint32_t mD3 = moff | ((uint32_t)h.ctl[i] << 8) | (bswap16u(h.window[i]) << 16);
+        uint32_t mD3 = moff | ((uint32_t)h.ctl[i] << 8) | (bswap16u(h.window[i]) << 16);
         const uint32_t mD4 = bswap16u(h.urgent[i]) << 16;  // checksum field (bytes 16-17) = 0 for the sum
-        const uint64_t mdb = data_off[i], mde = data_off[i + 1], moo = out_off[i];
+        uint64_t mdb = data_off[i], mde = data_off[i + 1];
+        const uint64_t moo = out_off[fr];
+        if constexpr (TSO) {  // the frame's slice, inside [db, de) whatever the frame map says
+            const uint64_t se = max(mde, mdb);
+            mdb = min(mdb + (uint64_t)tj * tmss, se);
+            mde = min(mdb + tmss, se);
+            mD1 = bswap32u(h.seq[i] + tj * tmss);
+            // control (byte 13): FIN and PSH on the last frame only, CWR on the first only
+            mD3 &= ~(((mde == se ? 0u : 0x09u) | (tj == 0 ? 0u : 0x80u)) << 8);
+        }
         uint32_t mpart = partial ? partial[i] : 0u;
         // frame positions: IPH ahead of the TCP header
         const uint32_t mhdr = IPH + 20u + moptlen + (moptlen ? (20u + moptlen) % 4u : 0u);  // tcp.go:118-121
@@ -2678,7 +2731,10 @@ __global__ __launch_bounds__(kBlock) void tcp_build_kernel(TcpHdrSoA h, const ui
             }
             if constexpr (IPH == 20) {
                 mI[0] = 0x45u | (bswap16u(20u + tl) << 16);
-                mI[1] = (ip.ident ? bswap16u(ip.ident[i]) : 0u) | (0x40u << 16);  // DF, fragment offset 0
+                if constexpr (TSO)  // ident + j modulo 2^16
+                    mI[1] = bswap16u(((ip.ident ? (uint32_t)ip.ident[i] : 0u) + tj) & 0xFFFFu) | (0x40u << 16);
+                else
+                    mI[1] = (ip.ident ? bswap16u(ip.ident[i]) : 0u) | (0x40u << 16);  // DF, fragment offset 0
                 mI[2] = ttl | (6u << 8);
                 mI[3] = a[0], mI[4] = a[1];
                 uint32_t hs = 0, as = 0;  // LE half-sums: the header with its field 0; the addresses
@@ -3952,11 +4008,13 @@ hipError_t launch_verify_mask(const uint16_t* raw, uint64_t n, uint64_t* mask, u
 
 constexpr uint64_t kBuildGroupBytes = 24576;  // images per TCP build wave task, about
 
-// ip: the transmit pass's IP fields (ipver 4 or 6); null = TCP images only (ipver ignored, partial as given)
-hipError_t launch_tcp_build(const LaunchCfg& c, int ipver, const IpHdrSoA* ip, const TcpHdrSoA& h,
-                            const uint8_t* opts, const uint64_t* opt_off, const uint8_t* data,
-                            const uint64_t* data_off, uint64_t data_bytes, const uint32_t* partial, uint64_t n,
-                            uint8_t* out, const uint64_t* out_off, uint16_t* raw, hipStream_t st) {
+// ip: the transmit pass's IP fields (ipver 4 or 6); null = TCP images only (ipver ignored, partial as given).
+// tso (with ip): segmentation offload — the field, option and data_off arrays are per super-segment, n counts
+// frames (out_off, raw), and the group size and chunk deal follow the frames as they do for per-frame arrays.
+static hipError_t launch_build(const LaunchCfg& c, int ipver, const IpHdrSoA* ip, const TsoMap* tso,
+                               const TcpHdrSoA& h, const uint8_t* opts, const uint64_t* opt_off, const uint8_t* data,
+                               const uint64_t* data_off, uint64_t data_bytes, const uint32_t* partial, uint64_t n,
+                               uint8_t* out, const uint64_t* out_off, uint16_t* raw, hipStream_t st) {
     // Path by layout: groups of ≤ 2-row images software-pipelined (the fast composition when every segment of
     // the group allows it, else the general one); longer images unpipelined. kernel 2 forces the unpipelined
     // path, kernel 3 the general pipelined composition (test coverage of those paths on every layout).
@@ -3977,6 +4035,18 @@ hipError_t launch_tcp_build(const LaunchCfg& c, int ipver, const IpHdrSoA* ip, c
     const uint32_t grid = grid_for(tasks, max_blocks);
     const uint32_t clog = deal_clog(c.xcd_chunk, tasks, (uint64_t)group * 2u * wire);  // payload + image per segment
     const int pipe = c.kernel == 2 ? 0 : c.kernel == 3 ? 2 : 1;
+    if (ip && tso) {
+#define NSX_TSO_LAUNCH(IPH, OPT)                                                                                  \
+    hipLaunchKernelGGL((tcp_build_kernel<0, 0, 2, OPT, IPH, true>), dim3(grid), dim3(kBlock), 0, st, h, opts,      \
+                       opt_off, data, data_off, data_bytes, nullptr, n, out, out_off, raw, group, clog, pipe,      \
+                       IpArgs<IPH, true>{{*ip}, tso->mss, tso->frame_first, tso->frame_seg})
+        if (ipver == 4 && opt_off) NSX_TSO_LAUNCH(20, true);
+        else if (ipver == 4) NSX_TSO_LAUNCH(20, false);
+        else if (opt_off) NSX_TSO_LAUNCH(40, true);
+        else NSX_TSO_LAUNCH(40, false);
+#undef NSX_TSO_LAUNCH
+        return hipGetLastError();
+    }
     if (ip) {
 #define NSX_TX_LAUNCH(IPH, OPT)                                                                                   \
     hipLaunchKernelGGL((tcp_build_kernel<0, 0, 2, OPT, IPH>), dim3(grid), dim3(kBlock), 0, st, h, opts, opt_off,   \
@@ -3995,6 +4065,22 @@ hipError_t launch_tcp_build(const LaunchCfg& c, int ipver, const IpHdrSoA* ip, c
         hipLaunchKernelGGL((tcp_build_kernel<0, 0, 2, false>), dim3(grid), dim3(kBlock), 0, st, h, opts, opt_off, data,
                            data_off, data_bytes, partial, n, out, out_off, raw, group, clog, pipe, IpArgs<0>{});
     return hipGetLastError();
+}
+
+hipError_t launch_tcp_build(const LaunchCfg& c, int ipver, const IpHdrSoA* ip, const TcpHdrSoA& h,
+                            const uint8_t* opts, const uint64_t* opt_off, const uint8_t* data,
+                            const uint64_t* data_off, uint64_t data_bytes, const uint32_t* partial, uint64_t n,
+                            uint8_t* out, const uint64_t* out_off, uint16_t* raw, hipStream_t st) {
+    return launch_build(c, ipver, ip, nullptr, h, opts, opt_off, data, data_off, data_bytes, partial, n, out, out_off,
+                        raw, st);
+}
+
+hipError_t launch_tso_build(const LaunchCfg& c, int ipver, const IpHdrSoA& ip, const TsoMap& tso, const TcpHdrSoA& h,
+                            const uint8_t* opts, const uint64_t* opt_off, const uint8_t* data,
+                            const uint64_t* data_off, uint64_t data_bytes, uint64_t n_frames, uint8_t* out,
+                            const uint64_t* out_off, uint16_t* raw, hipStream_t st) {
+    return launch_build(c, ipver, &ip, &tso, h, opts, opt_off, data, data_off, data_bytes, nullptr, n_frames, out,
+                        out_off, raw, st);
 }
 
 // Headers per launch of the packed 20 B header kernel. Like the fixed path's windows (fixed_window), a batch

@@ -363,6 +363,11 @@ int run_sharded(const uint8_t* h_base, uint64_t stride, uint32_t seg_len, const 
 // kernel path it would take in a device-resident batch at a 256-aligned base.
 // The transmit pass (nsx_tx_ipv4_tcp_build_host / nsx_tx_ipv6_tcp_build_host) is the same job with an IP part: its
 // six nsx_ip_hdr_soa arrays ride in the field block behind the TCP fields, and the kernel writes whole datagrams.
+// Segmentation offload (nsx_tso_ipv4_tcp_build_host / nsx_tso_ipv6_tcp_build_host) is the transmit job over super-
+// segments: shards and chunks are ranges of super-segments [c0, c1), whose fields (with their mss as a 15th field
+// array), options and payload are staged once each; the chunk's frames [frame_first[c0], frame_first[c1]) own its
+// image span and raw sums, and the frame map goes along rebased — frame_first less frame_first[c0] behind the
+// offsets, frame_seg rebuilt from it as chunk-local indices.
 struct BuildJob {
     const nsx_ip_hdr_soa* ip;  // host arrays; null = TCP images only
     int ipver;                 // 4 or 6 with ip
@@ -376,6 +381,11 @@ struct BuildJob {
     const uint64_t* out_off;
     uint16_t* raw;  // nullable
     bool gaps;      // some image slot is longer than its 4-padded image: the caller's bytes there are preserved
+    // segmentation offload (mss non-null): every array above but out_off and raw is per super-segment
+    const uint32_t* mss;
+    const uint64_t* frame_first;  // n + 1
+    const uint64_t* seg_out;      // image offset of each segment's / super-segment's first frame (n + 1): what shards
+                                  // and chunks are cut by; out_off itself without segmentation
     uint64_t lo, hi;
     int dev, slot;
     const nsx_tune* tune;
@@ -384,10 +394,10 @@ struct BuildJob {
 
 constexpr uint64_t kFieldAlign = 256;
 
-constexpr int kTcpFields = 8, kIpFields = 6;
+constexpr int kTcpFields = 8, kIpFields = 6, kAllFields = kTcpFields + kIpFields + 1;
 
-// The job's field arrays (null where the caller passed none) and their entry sizes: 8 TCP, then 6 IP.
-int field_arrays(const BuildJob& j, const void* (&src)[kTcpFields + kIpFields], uint64_t (&esz)[kTcpFields + kIpFields]) {
+// The job's field arrays (null where the caller passed none) and their entry sizes: 8 TCP, then 6 IP, then the mss.
+int field_arrays(const BuildJob& j, const void* (&src)[kAllFields], uint64_t (&esz)[kAllFields]) {
     const void* t[kTcpFields] = {j.h->src_port, j.h->dst_port,   j.h->seq_num, j.h->ack_num,
                                  j.h->window,   j.h->urgent_ptr, j.h->offset,  j.h->control};
     const uint64_t ts[kTcpFields] = {2, 2, 4, 4, 2, 2, 1, 1};
@@ -397,12 +407,14 @@ int field_arrays(const BuildJob& j, const void* (&src)[kTcpFields + kIpFields], 
     const void* a[kIpFields] = {j.ip->src, j.ip->dst, j.ip->ident, j.ip->ttl, j.ip->tclass, j.ip->flow};
     const uint64_t as[kIpFields] = {alen, alen, 2, 1, 1, 4};
     for (int f = 0; f < kIpFields; ++f) src[kTcpFields + f] = a[f], esz[kTcpFields + f] = as[f];
-    return kTcpFields + kIpFields;
+    if (!j.mss) return kTcpFields + kIpFields;
+    src[kTcpFields + kIpFields] = j.mss, esz[kTcpFields + kIpFields] = 4;
+    return kAllFields;
 }
 
 uint64_t field_block_bytes(const BuildJob& j, uint64_t cn) {  // sub-arrays of cn entries, each 256 B-aligned
-    const void* src[kTcpFields + kIpFields];
-    uint64_t esz[kTcpFields + kIpFields], at = 0;
+    const void* src[kAllFields];
+    uint64_t esz[kAllFields], at = 0;
     const int nf = field_arrays(j, src, esz);
     for (int f = 0; f < nf; ++f) at += (cn * esz[f] + kFieldAlign - 1) & ~(kFieldAlign - 1);
     return at;
@@ -411,20 +423,25 @@ uint64_t field_block_bytes(const BuildJob& j, uint64_t cn) {  // sub-arrays of c
 void run_build_job(BuildJob* j) {
     int rc = NSX_OK;
     std::vector<Chunk> chunks;  // byte_lo/byte_hi: the chunk's image span
+    const uint64_t budget = j->tune && j->tune->chunk_bytes > 0 ? (uint64_t)j->tune->chunk_bytes : kChunkBytes;
     for (uint64_t c0 = j->lo; c0 < j->hi;) {
         uint64_t c1 = c0 + 1;
-        while (c1 < j->hi && j->out_off[c1 + 1] - j->out_off[c0] <= kChunkBytes &&
-               j->data_off[c1 + 1] - j->data_off[c0] <= kChunkBytes)
+        while (c1 < j->hi && j->seg_out[c1 + 1] - j->seg_out[c0] <= budget &&
+               j->data_off[c1 + 1] - j->data_off[c0] <= budget)
             ++c1;
-        chunks.push_back({c0, c1, j->out_off[c0], j->out_off[c1]});
+        chunks.push_back({c0, c1, j->seg_out[c0], j->seg_out[c1]});
         c0 = c1;
     }
-    uint64_t max_out = 0, max_data = 0, max_opt = 0, max_segs = 0;
+    const bool tso = j->mss != nullptr;
+    // the frames of segments [c0, c1): the segments themselves without segmentation
+    auto frame_at = [j, tso](uint64_t c) { return tso ? j->frame_first[c] : c; };
+    uint64_t max_out = 0, max_data = 0, max_opt = 0, max_segs = 0, max_frames = 0;
     for (const Chunk& c : chunks) {
         max_out = std::max(max_out, c.byte_hi - c.byte_lo);
         max_data = std::max(max_data, j->data_off[c.c1] - j->data_off[c.c0]);
         if (j->opt_off) max_opt = std::max(max_opt, j->opt_off[c.c1] - j->opt_off[c.c0]);
         max_segs = std::max(max_segs, c.c1 - c.c0);
+        max_frames = std::max(max_frames, frame_at(c.c1) - frame_at(c.c0));
     }
     const bool in_pinned = is_pinned(j->data), out_pinned = is_pinned(j->out);
     const int nslots = chunks.size() > 1 ? 2 : 1;
@@ -437,14 +454,20 @@ void run_build_job(BuildJob* j) {
     hipStream_t* st = ctx->st;
     nsx::LaunchCfg cfg;
     const Chunk* pending[2] = {nullptr, nullptr};
-    const uint64_t noffs = j->opt_off ? 3 : 2;  // rebased data_off, out_off (, opt_off), cn + 1 entries each
+    // rebased offsets in one block: data_off (cn + 1), out_off (fn + 1), then opt_off (cn + 1) when given; with
+    // segmentation also frame_first (cn + 1) and frame_seg (fn 4-byte entries) — cn segments, fn frames
+    auto off_words = [j, tso](uint64_t cn, uint64_t fn) {
+        return (cn + 1) + (fn + 1) + (j->opt_off ? cn + 1 : 0) + (tso ? (cn + 1) + (fn + 1) / 2 : 0);
+    };
     auto finish = [&](int s) {  // chunk pending[s] is complete on the device: hand its results to the caller
         const Chunk* c = pending[s];
         const uint64_t lead_o = c->byte_lo & 255;
         // the images back into pageable caller memory: the same multi-threaded copy as the payloads' way in (one
         // thread's memcpy held the pageable build at 31.7 GB/s of PCIe traffic against 54.3 pinned)
         if (!out_pinned) stage_copy(j->out + c->byte_lo, ctx->h_ostage[s].as<uint8_t>() + lead_o, c->byte_hi - c->byte_lo);
-        if (j->raw) std::memcpy(j->raw + c->c0, ctx->h_rawstage[s].p, (c->c1 - c->c0) * sizeof(uint16_t));
+        if (j->raw)
+            std::memcpy(j->raw + frame_at(c->c0), ctx->h_rawstage[s].p,
+                        (frame_at(c->c1) - frame_at(c->c0)) * sizeof(uint16_t));
         pending[s] = nullptr;
     };
 
@@ -456,10 +479,10 @@ void run_build_job(BuildJob* j) {
         NSX_TRY(ctx->d_out[s].ensure(256 + max_out + 16));
         NSX_TRY(ctx->d_fields[s].ensure(field_block_bytes(*j, max_segs)));
         NSX_TRY(ctx->h_fstage[s].ensure(field_block_bytes(*j, max_segs)));
-        NSX_TRY(ctx->d_off[s].ensure(noffs * (max_segs + 1) * sizeof(uint64_t)));
-        NSX_TRY(ctx->h_offstage[s].ensure(noffs * (max_segs + 1) * sizeof(uint64_t)));
-        NSX_TRY(ctx->d_raw[s].ensure(std::max<uint64_t>(max_segs * sizeof(uint16_t), 16)));
-        NSX_TRY(ctx->h_rawstage[s].ensure(std::max<uint64_t>(max_segs * sizeof(uint16_t), 16)));
+        NSX_TRY(ctx->d_off[s].ensure(off_words(max_segs, max_frames) * sizeof(uint64_t)));
+        NSX_TRY(ctx->h_offstage[s].ensure(off_words(max_segs, max_frames) * sizeof(uint64_t)));
+        NSX_TRY(ctx->d_raw[s].ensure(std::max<uint64_t>(max_frames * sizeof(uint16_t), 16)));
+        NSX_TRY(ctx->h_rawstage[s].ensure(std::max<uint64_t>(max_frames * sizeof(uint16_t), 16)));
         if (j->partial) {
             NSX_TRY(ctx->d_part[s].ensure(max_segs * sizeof(uint32_t)));
             NSX_TRY(ctx->h_pstage[s].ensure(max_segs * sizeof(uint32_t)));
@@ -476,6 +499,7 @@ void run_build_job(BuildJob* j) {
         const int s = (int)(k % nslots);
         const Chunk& c = chunks[k];
         const uint64_t cn = c.c1 - c.c0, span_o = c.byte_hi - c.byte_lo;
+        const uint64_t f0 = frame_at(c.c0), fn = frame_at(c.c1) - f0;
         const uint64_t d0 = j->data_off[c.c0], span_d = j->data_off[c.c1] - d0;
         const uint64_t lead_d = 256 + (d0 & 255), lead_o = c.byte_lo & 255;
         if (pending[s]) {  // slot reuse: finish chunk k-2
@@ -485,10 +509,10 @@ void run_build_job(BuildJob* j) {
         // header fields: the sub-arrays in one pinned block, one copy
         uint8_t* hf = ctx->h_fstage[s].as<uint8_t>();
         uint8_t* df = ctx->d_fields[s].as<uint8_t>();
-        const void* src_f[kTcpFields + kIpFields];
-        uint64_t esz[kTcpFields + kIpFields];
+        const void* src_f[kAllFields];
+        uint64_t esz[kAllFields];
         const int nf = field_arrays(*j, src_f, esz);
-        const void* dev_f[kTcpFields + kIpFields] = {};
+        const void* dev_f[kAllFields] = {};
         uint64_t at = 0;
         for (int f = 0; f < nf; ++f) {
             dev_f[f] = src_f[f] ? df + at : nullptr;
@@ -499,12 +523,20 @@ void run_build_job(BuildJob* j) {
         // offsets, rebased to the staged spans
         uint64_t* ho = ctx->h_offstage[s].as<uint64_t>();
         uint64_t* dofs = ctx->d_off[s].as<uint64_t>();
+        const uint64_t at_out = cn + 1, at_opt = at_out + fn + 1, at_first = at_opt + (j->opt_off ? cn + 1 : 0),
+                       at_seg = at_first + cn + 1;
         for (uint64_t i = 0; i <= cn; ++i) {
             ho[i] = j->data_off[c.c0 + i] - d0 + lead_d;
-            ho[cn + 1 + i] = j->out_off[c.c0 + i] - c.byte_lo + lead_o;
-            if (j->opt_off) ho[2 * (cn + 1) + i] = j->opt_off[c.c0 + i] - j->opt_off[c.c0];
+            if (j->opt_off) ho[at_opt + i] = j->opt_off[c.c0 + i] - j->opt_off[c.c0];
+            if (tso) ho[at_first + i] = j->frame_first[c.c0 + i] - f0;
         }
-        NSX_TRY(hipMemcpyAsync(dofs, ho, noffs * (cn + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st[s]));
+        for (uint64_t i = 0; i <= fn; ++i) ho[at_out + i] = j->out_off[f0 + i] - c.byte_lo + lead_o;
+        if (tso) {
+            uint32_t* seg = reinterpret_cast<uint32_t*>(ho + at_seg);
+            for (uint64_t i = 0; i < cn; ++i)
+                for (uint64_t f = j->frame_first[c.c0 + i]; f < j->frame_first[c.c0 + i + 1]; ++f) seg[f - f0] = (uint32_t)i;
+        }
+        NSX_TRY(hipMemcpyAsync(dofs, ho, off_words(cn, fn) * sizeof(uint64_t), hipMemcpyHostToDevice, st[s]));
         const uint8_t* d_opts = nullptr;
         if (j->opt_off) {
             const uint64_t ospan = j->opt_off[c.c1] - j->opt_off[c.c0];
@@ -542,12 +574,20 @@ void run_build_job(BuildJob* j) {
         const nsx::IpHdrSoA ipd{(const uint8_t*)dev_f[8],  (const uint8_t*)dev_f[9],  (const uint16_t*)dev_f[10],
                                 (const uint8_t*)dev_f[11], (const uint8_t*)dev_f[12], (const uint32_t*)dev_f[13]};
         uint16_t* d_raw = ctx->d_raw[s].as<uint16_t>();
-        NSX_TRY(nsx::launch_tcp_build(cfg, j->ipver, j->ip ? &ipd : nullptr, h, d_opts,
-                                      j->opt_off ? dofs + 2 * (cn + 1) : nullptr, d_data, dofs, lead_d + span_d, d_part,
-                                      cn, d_out, dofs + cn + 1, j->raw ? d_raw : nullptr, st[s]));
+        if (tso) {
+            const nsx::TsoMap map{(const uint32_t*)dev_f[kTcpFields + kIpFields], dofs + at_first,
+                                  reinterpret_cast<const uint32_t*>(dofs + at_seg)};
+            NSX_TRY(nsx::launch_tso_build(cfg, j->ipver, ipd, map, h, d_opts, j->opt_off ? dofs + at_opt : nullptr,
+                                          d_data, dofs, lead_d + span_d, fn, d_out, dofs + at_out,
+                                          j->raw ? d_raw : nullptr, st[s]));
+        } else {
+            NSX_TRY(nsx::launch_tcp_build(cfg, j->ipver, j->ip ? &ipd : nullptr, h, d_opts,
+                                          j->opt_off ? dofs + at_opt : nullptr, d_data, dofs, lead_d + span_d, d_part,
+                                          cn, d_out, dofs + at_out, j->raw ? d_raw : nullptr, st[s]));
+        }
         if (span_o) NSX_TRY(hipMemcpyAsync(out_dst, d_out + lead_o, span_o, hipMemcpyDeviceToHost, st[s]));
         if (j->raw)
-            NSX_TRY(hipMemcpyAsync(ctx->h_rawstage[s].p, d_raw, cn * sizeof(uint16_t), hipMemcpyDeviceToHost, st[s]));
+            NSX_TRY(hipMemcpyAsync(ctx->h_rawstage[s].p, d_raw, fn * sizeof(uint16_t), hipMemcpyDeviceToHost, st[s]));
         pending[s] = &c;
     }
     for (int s = 0; s < nslots; ++s) {
@@ -570,7 +610,7 @@ int run_build_sharded(const BuildJob& proto, uint64_t n, int num_gpus, const nsx
     }
     if (count <= 0) return NSX_ENODEV;
     if (num_gpus <= 0) {  // auto: all GPUs, but no shard smaller than one chunk of images
-        const uint64_t bytes = proto.out_off[n] - proto.out_off[0];
+        const uint64_t bytes = proto.seg_out[n] - proto.seg_out[0];
         const uint64_t want = std::max<uint64_t>(1, (bytes + kChunkBytes - 1) / kChunkBytes);
         num_gpus = (int)std::min<uint64_t>(want, (uint64_t)count);
     }
@@ -580,7 +620,7 @@ int run_build_sharded(const BuildJob& proto, uint64_t n, int num_gpus, const nsx
     (void)hipGetDevice(&caller_dev);
     const int parts = (int)std::min<uint64_t>((uint64_t)num_gpus * spd, n);
     std::vector<uint64_t> bounds(parts + 1);
-    nsx::shard_plan(proto.out_off, n, parts, bounds.data());  // balanced by image bytes
+    nsx::shard_plan(proto.seg_out, n, parts, bounds.data());  // balanced by image bytes
     std::vector<BuildJob> jobs(parts, proto);
     for (int g = 0; g < parts; ++g) {
         jobs[g].lo = bounds[g], jobs[g].hi = bounds[g + 1];
@@ -622,8 +662,49 @@ int build_host(const nsx_ip_hdr_soa* ip, int ipver, const nsx_tcp_hdr_soa* h_hdr
         if (wire > wire_max || slot >= (1ull << 31) || h_out_off[i + 1] - h_out_off[i] < slot) return NSX_EINVAL;
         gaps |= h_out_off[i + 1] - h_out_off[i] > slot;
     }
-    const BuildJob proto{ip,   ipver, h_hdr, h_opts, h_opt_off, h_data, h_data_off, h_prefix_partial, h_out, h_out_off,
-                         h_raw, gaps, 0,     0,      0,         0,      tune,       NSX_OK};
+    const BuildJob proto{ip,   ipver, h_hdr,   h_opts,  h_opt_off, h_data, h_data_off, h_prefix_partial, h_out, h_out_off,
+                         h_raw, gaps, nullptr, nullptr, h_out_off, 0,      0,          0,                0,     tune,
+                         NSX_OK};
+    return run_build_sharded(proto, n, num_gpus, tune);
+}
+
+// The segmentation offload host calls: everything the chunks rely on is checked here, before any copy.
+int tso_build_host(const nsx_ip_hdr_soa* ip, int ipver, const nsx_tcp_hdr_soa* h_hdr, const uint8_t* h_opts,
+                   const uint64_t* h_opt_off, const uint8_t* h_data, const uint64_t* h_data_off, const uint32_t* h_mss,
+                   uint64_t n, const uint64_t* h_frame_first, const uint32_t* h_frame_seg, uint64_t n_frames,
+                   uint8_t* h_out, const uint64_t* h_out_off, uint16_t* h_raw, int num_gpus, const nsx_tune* tune) {
+    if (n_frames == 0) return NSX_OK;
+    if (n == 0 || n >= (1ull << 32) || !ip || !ip->src || !ip->dst || !h_hdr || !h_hdr->src_port || !h_hdr->dst_port ||
+        !h_hdr->seq_num || !h_hdr->ack_num || !h_hdr->control || !h_hdr->window || !h_hdr->urgent_ptr || !h_data_off ||
+        !h_mss || !h_frame_first || !h_frame_seg || !h_out || !h_out_off || (h_opt_off && !h_opts))
+        return NSX_EINVAL;
+    if (h_data_off[n] > h_data_off[0] && !h_data) return NSX_EINVAL;
+    const uint64_t iph = ipver == 4 ? 20 : 40, wire_max = ipver == 4 ? 65515 : 65535;
+    std::vector<uint64_t> seg_out(n + 1);
+    bool gaps = false;
+    uint64_t f = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (h_mss[i] == 0 || h_data_off[i + 1] < h_data_off[i] || (h_opt_off && h_opt_off[i + 1] < h_opt_off[i]) ||
+            h_frame_first[i] != f)
+            return NSX_EINVAL;
+        const uint64_t ol = h_opt_off ? h_opt_off[i + 1] - h_opt_off[i] : 0;
+        const uint64_t len = h_data_off[i + 1] - h_data_off[i], cnt = len ? (len + h_mss[i] - 1) / h_mss[i] : 1;
+        if (cnt > n_frames - f) return NSX_EINVAL;
+        seg_out[i] = h_out_off[f];
+        for (uint64_t k = 0; k < cnt; ++k, ++f) {
+            const uint64_t wire = nsx_tcp_wire_len(ol, std::min<uint64_t>(h_mss[i], len - k * h_mss[i]));
+            const uint64_t slot = (iph + wire + 3) & ~3ull;
+            if (h_frame_seg[f] != i || h_out_off[f + 1] < h_out_off[f] || (h_out_off[f] & 3) || wire > wire_max ||
+                h_out_off[f + 1] - h_out_off[f] < slot)
+                return NSX_EINVAL;
+            gaps |= h_out_off[f + 1] - h_out_off[f] > slot;
+        }
+    }
+    if (f != n_frames || h_frame_first[n] != n_frames) return NSX_EINVAL;
+    seg_out[n] = h_out_off[n_frames];
+    const BuildJob proto{ip,   ipver, h_hdr, h_opts,        h_opt_off,      h_data, h_data_off, nullptr, h_out, h_out_off,
+                         h_raw, gaps, h_mss, h_frame_first, seg_out.data(), 0,      0,          0,       0,     tune,
+                         NSX_OK};
     return run_build_sharded(proto, n, num_gpus, tune);
 }
 
@@ -738,6 +819,28 @@ int nsx_tx_ipv6_tcp_build_host_tuned(const nsx_ip_hdr_soa* h_ip, const nsx_tcp_h
     return build_host(h_ip, 6, h_tcp, h_opts, h_opt_off, h_data, h_data_off, nullptr, n, h_out, h_out_off, h_tcp_raw,
                       num_gpus, tune);
 }
+
+#define NSX_TSO_HOST(V)                                                                                             \
+    int nsx_tso_ipv##V##_tcp_build_host_tuned(                                                                      \
+        const nsx_ip_hdr_soa* h_ip, const nsx_tcp_hdr_soa* h_tcp, const uint8_t* h_opts, const uint64_t* h_opt_off, \
+        const uint8_t* h_data, const uint64_t* h_data_off, const uint32_t* h_mss, uint64_t n,                       \
+        const uint64_t* h_frame_first, const uint32_t* h_frame_seg, uint64_t n_frames, uint8_t* h_out,              \
+        const uint64_t* h_out_off, uint16_t* h_tcp_raw, int num_gpus, const nsx_tune* tune) {                       \
+        return tso_build_host(h_ip, V, h_tcp, h_opts, h_opt_off, h_data, h_data_off, h_mss, n, h_frame_first,        \
+                              h_frame_seg, n_frames, h_out, h_out_off, h_tcp_raw, num_gpus, tune);                  \
+    }                                                                                                               \
+    int nsx_tso_ipv##V##_tcp_build_host(                                                                            \
+        const nsx_ip_hdr_soa* h_ip, const nsx_tcp_hdr_soa* h_tcp, const uint8_t* h_opts, const uint64_t* h_opt_off, \
+        const uint8_t* h_data, const uint64_t* h_data_off, const uint32_t* h_mss, uint64_t n,                       \
+        const uint64_t* h_frame_first, const uint32_t* h_frame_seg, uint64_t n_frames, uint8_t* h_out,              \
+        const uint64_t* h_out_off, uint16_t* h_tcp_raw, int num_gpus) {                                             \
+        return nsx_tso_ipv##V##_tcp_build_host_tuned(h_ip, h_tcp, h_opts, h_opt_off, h_data, h_data_off, h_mss, n,   \
+                                                     h_frame_first, h_frame_seg, n_frames, h_out, h_out_off,        \
+                                                     h_tcp_raw, num_gpus, nullptr);                                 \
+    }
+NSX_TSO_HOST(4)
+NSX_TSO_HOST(6)
+#undef NSX_TSO_HOST
 
 int nsx_host_cache_release(void) {
     std::lock_guard<std::mutex> g(g_ctx_mu);

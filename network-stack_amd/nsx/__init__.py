@@ -30,7 +30,7 @@ class Tune(ctypes.Structure):
                 ("block_mode", ctypes.c_int32), ("rows", ctypes.c_int32), ("run_segs", ctypes.c_int32),
                 ("xcd_chunk", ctypes.c_int32), ("window_bytes", ctypes.c_int64), ("kernel", ctypes.c_int32),
                 ("shards_per_device", ctypes.c_int32), ("deal", ctypes.c_int32),
-                ("reserved", ctypes.c_int32 * 5)]
+                ("chunk_bytes", ctypes.c_int32), ("reserved", ctypes.c_int32 * 4)]
 
 
 TUNE_FIELDS = tuple(f for f, _ in Tune._fields_ if f != "reserved")
@@ -117,12 +117,23 @@ def lib() -> ctypes.CDLL:
             "nsx_tx_ipv6_tcp_build_host": [vp, vp, vp, vp, vp, vp, u64, vp, vp, vp, i32],
             "nsx_tx_ipv4_tcp_build_host_tuned": [vp, vp, vp, vp, vp, vp, u64, vp, vp, vp, i32, vp],
             "nsx_tx_ipv6_tcp_build_host_tuned": [vp, vp, vp, vp, vp, vp, u64, vp, vp, vp, i32, vp],
+            "nsx_tso_count_host": [vp, vp, u64, vp],
+            "nsx_tso_layout_host": [vp, vp, vp, vp, u64, u32, vp, vp],
+            "nsx_tso_ipv4_tcp_build_dev": [vp, vp, vp, vp, vp, vp, u64, vp, u64, vp, vp, u64, vp, vp, vp, vp],
+            "nsx_tso_ipv6_tcp_build_dev": [vp, vp, vp, vp, vp, vp, u64, vp, u64, vp, vp, u64, vp, vp, vp, vp],
+            "nsx_tso_ipv4_tcp_build_dev_tuned": [vp, vp, vp, vp, vp, vp, u64, vp, u64, vp, vp, u64, vp, vp, vp, vp, vp],
+            "nsx_tso_ipv6_tcp_build_dev_tuned": [vp, vp, vp, vp, vp, vp, u64, vp, u64, vp, vp, u64, vp, vp, vp, vp, vp],
+            "nsx_tso_ipv4_tcp_build_host": [vp, vp, vp, vp, vp, vp, vp, u64, vp, vp, u64, vp, vp, vp, i32],
+            "nsx_tso_ipv6_tcp_build_host": [vp, vp, vp, vp, vp, vp, vp, u64, vp, vp, u64, vp, vp, vp, i32],
+            "nsx_tso_ipv4_tcp_build_host_tuned": [vp, vp, vp, vp, vp, vp, vp, u64, vp, vp, u64, vp, vp, vp, i32, vp],
+            "nsx_tso_ipv6_tcp_build_host_tuned": [vp, vp, vp, vp, vp, vp, vp, u64, vp, vp, u64, vp, vp, vp, i32, vp],
             "nsx_fixed_launch_count": [u64, u32, u64, vp, ctypes.POINTER(u64)],
             "nsx_ipv4_hdr_launch_count": [vp, u64, u32, u64, vp, ctypes.POINTER(u64)],
         }
         # present since ABI round 6, and the transmit pass since its own change; an older library (same-box A/B against a
         # previous build) lacks them
-        optional = {"nsx_stream_release", "nsx_deal_sets_in_use"} | {k for k in sig if k.startswith("nsx_tx_")}
+        optional = {"nsx_stream_release", "nsx_deal_sets_in_use"} | \
+            {k for k in sig if k.startswith(("nsx_tx_", "nsx_tso_"))}
         for name, args in sig.items():
             if name in optional and not hasattr(L, name):
                 continue
@@ -745,6 +756,200 @@ def tx_ipv6_tcp_build_host(ip: dict, fields: dict, data: np.ndarray, data_off: n
                            opt_off: np.ndarray | None = None, out: np.ndarray | None = None, want_raw: bool = True,
                            num_gpus: int = 0, tune=None):
     return _tx_build_host(6, ip, fields, data, data_off, out_off, opts, opt_off, out, want_raw, num_gpus, tune)
+
+
+# ---------------------------------------------------------------------------
+# segmentation offload on the transmit pass: super-segments in, frames out (nsx_tso_*)
+# ---------------------------------------------------------------------------
+def _tso_host_args(data_off, mss, what: str):
+    data_off = np.ascontiguousarray(data_off, np.uint64)
+    n = data_off.size - 1
+    if n < 0:
+        raise ValueError(f"{what} data_off: needs n + 1 entries")
+    mss = np.ascontiguousarray(mss, np.uint32)
+    if mss.size < n:
+        raise ValueError(f"{what} mss: {mss.size} entries for {n} super-segments")
+    return data_off, mss, n
+
+
+def tso_count_host(data_off: np.ndarray, mss: np.ndarray) -> np.ndarray:
+    """nsx_tso_count_host: frame_first (n + 1), the prefix sum of max(1, ceil(len_s / mss_s)); frame_first[n] is the
+    batch's frame count."""
+    data_off, mss, n = _tso_host_args(data_off, mss, "tso_count_host")
+    first = np.zeros(n + 1, np.uint64)
+    _check(lib().nsx_tso_count_host(_np_ptr(data_off), _np_ptr(mss), n, _np_ptr(first)), "nsx_tso_count_host")
+    return first
+
+
+def tso_layout_host(data_off: np.ndarray, mss: np.ndarray, frame_first: np.ndarray,
+                    opt_off: np.ndarray | None = None, ip_hdr_len: int = 20):
+    """nsx_tso_layout_host: (frame_seg[n_frames], out_off[n_frames + 1]) — each frame's super-segment and the packed
+    4-aligned frame slots of the expanded batch."""
+    data_off, mss, n = _tso_host_args(data_off, mss, "tso_layout_host")
+    first = np.ascontiguousarray(frame_first, np.uint64)
+    if first.size < n + 1:
+        raise ValueError(f"tso_layout_host frame_first: {first.size} entries for {n} super-segments")
+    oo = None if opt_off is None else np.ascontiguousarray(opt_off, np.uint64)
+    if oo is not None and oo.size < n + 1:
+        raise ValueError(f"tso_layout_host opt_off: {oo.size} entries for {n} super-segments")
+    # the C call checks frame_first against its own count before it writes: these sizes hold whenever it writes
+    nf = int(first[n])
+    if nf >= 1 << 40:
+        raise ValueError(f"tso_layout_host frame_first: {nf} frames")
+    seg = np.zeros(max(nf, 1), np.uint32)
+    out = np.zeros(nf + 1, np.uint64)
+    _check(lib().nsx_tso_layout_host(_np_ptr(oo), _np_ptr(data_off), _np_ptr(mss), _np_ptr(first), n, ip_hdr_len,
+                                     _np_ptr(seg), _np_ptr(out)), "nsx_tso_layout_host")
+    return seg[:nf], out
+
+
+def _tso_build_dev(ipver: int, ip: dict, fields: dict, data, data_off, mss, frame_first, frame_seg, out, out_off, opts,
+                   opt_off, raw, stream, tune, n_frames):
+    what = f"tso_ipv{ipver}_tcp_build_dev"
+    n = _count(data_off, f"{what} data_off")
+    nf = _count(out_off, f"{what} out_off") if n_frames is None else int(n_frames)
+    if nf < 0:
+        raise ValueError(f"{what}: n_frames {nf}")
+    _span(frame_seg, 4 * nf, f"{what} frame_seg", elem=4)
+    sizes = _ip_sizes(ipver)
+    for k in ("src", "dst"):
+        if ip.get(k) is None:
+            raise ValueError(f"{what}: address array {k!r} missing")
+    for k in IP_FIELDS:
+        _span(ip.get(k), sizes[k] * n, f"{what} {k}", elem=None if k in ("src", "dst") else sizes[k])
+    for k, size in BUILD_FIELDS:
+        if fields.get(k) is None and k != "offset":  # only byte 12 may be computed on the device
+            raise ValueError(f"{what}: header field {k!r} missing")
+        _span(fields.get(k), size * n, f"{what} {k}", elem=size)
+    _span(data, 0, f"{what} data")
+    _span(mss, 4 * n, f"{what} mss", elem=4)
+    _span(frame_first, 8 * (n + 1), f"{what} frame_first", elem=8)
+    _span(out_off, 8 * (nf + 1), f"{what} out_off", elem=8)
+    if nf and (n <= 0 or nf < n):
+        raise ValueError(f"{what}: {nf} frames for {n} super-segments")
+    # the frame lengths are in device memory; the least a frame can take is an IP and a TCP header
+    _span(out, nf * (40 if ipver == 4 else 60), f"{what} out", elem=1)
+    _span(opt_off, 8 * (n + 1), f"{what} opt_off", elem=8)
+    if opt_off is not None and opts is None:
+        raise ValueError(f"{what}: opt_off given without opts")
+    _span(opts, 0, f"{what} opts")
+    _span(raw, 2 * nf, f"{what} raw", elem=2)
+    ipsoa = IpHdrSoA(*[_dev_ptr(ip.get(k)) for k in IP_FIELDS])
+    soa = TcpHdrSoA(*[_dev_ptr(fields.get(k)) for k, _ in BUILD_FIELDS])
+    fn = getattr(lib(), f"nsx_tso_ipv{ipver}_tcp_build_dev_tuned")
+    _check(fn(ctypes.byref(ipsoa), ctypes.byref(soa), _dev_ptr(opts), _dev_ptr(opt_off), _dev_ptr(data),
+              _dev_ptr(data_off), data.numel(), _dev_ptr(mss), max(n, 0), _dev_ptr(frame_first), _dev_ptr(frame_seg),
+              nf, _dev_ptr(out), _dev_ptr(out_off), _dev_ptr(raw), _stream(stream), _tune(tune)), f"nsx_{what}")
+    return out
+
+
+def tso_ipv4_tcp_build_dev(ip: dict, fields: dict, data, data_off, mss, frame_first, frame_seg, out, out_off,
+                           opts=None, opt_off=None, raw=None, stream=None, tune=None, n_frames=None):
+    """Segmentation offload on the transmit pass: ip, fields, opt_off, data_off and mss (uint32: payload bytes per
+    frame) hold one entry per super-segment; frame_first / frame_seg / out_off are the frame map of tso_count_host
+    and tso_layout_host as device tensors (frame_seg: one 4-byte entry per frame; out_off: one more — n_frames
+    defaults to its length less one). Frame j of a super-segment carries seq + j·mss, FIN / PSH only when last, CWR only when
+    first, ident + j. raw (optional): one TCP raw sum per frame."""
+    return _tso_build_dev(4, ip, fields, data, data_off, mss, frame_first, frame_seg, out, out_off, opts, opt_off, raw,
+                          stream, tune, n_frames)
+
+
+def tso_ipv6_tcp_build_dev(ip: dict, fields: dict, data, data_off, mss, frame_first, frame_seg, out, out_off,
+                           opts=None, opt_off=None, raw=None, stream=None, tune=None, n_frames=None):
+    """The same for IPv6 (flow label and traffic class copied to every frame)."""
+    return _tso_build_dev(6, ip, fields, data, data_off, mss, frame_first, frame_seg, out, out_off, opts, opt_off, raw,
+                          stream, tune, n_frames)
+
+
+def _tso_build_host(ipver: int, ip: dict, fields: dict, data, data_off, mss, frame_first, frame_seg, out_off, opts,
+                    opt_off, out, want_raw, num_gpus, tune):
+    what = f"tso_ipv{ipver}_tcp_build_host"
+    data = np.ascontiguousarray(data, np.uint8)
+    data_off, mss, n = _tso_host_args(data_off, mss, what)
+    sizes = _ip_sizes(ipver)
+    ipc = {}
+    for k in IP_FIELDS:
+        v = ip.get(k)
+        if v is None:
+            if k in ("src", "dst"):
+                raise ValueError(f"{what}: address array {k!r} missing")
+            continue
+        v = np.ascontiguousarray(v, _IP_NP[k])
+        if v.nbytes < sizes[k] * n:
+            raise ValueError(f"{what} {k}: {v.nbytes} B given, {sizes[k] * n} B needed")
+        ipc[k] = v
+    cols = {}
+    for k, _ in BUILD_FIELDS:
+        v = fields.get(k)
+        if v is None:
+            if k != "offset":
+                raise ValueError(f"{what}: header field {k!r} missing")
+            continue
+        v = np.ascontiguousarray(v, _BUILD_NP[k])
+        if v.size < n:
+            raise ValueError(f"{what} {k}: {v.size} entries for {n} super-segments")
+        cols[k] = v
+    oo = None if opt_off is None else np.ascontiguousarray(opt_off, np.uint64)
+    if oo is not None and opts is None:
+        raise ValueError(f"{what}: opt_off given without opts")
+    if oo is not None and oo.size < n + 1:
+        raise ValueError(f"{what} opt_off: {oo.size} entries for {n} super-segments")
+    ob = None if opts is None else (np.ascontiguousarray(opts, np.uint8) if len(opts) else np.zeros(1, np.uint8))
+    if frame_first is None:
+        frame_first = tso_count_host(data_off, mss)
+    first = np.ascontiguousarray(frame_first, np.uint64)
+    if first.size < n + 1:
+        raise ValueError(f"{what} frame_first: {first.size} entries for {n} super-segments")
+    if frame_seg is None or out_off is None:
+        seg0, off0 = tso_layout_host(data_off, mss, first, oo, 20 if ipver == 4 else 40)
+        frame_seg = seg0 if frame_seg is None else frame_seg
+        out_off = off0 if out_off is None else out_off
+    seg = np.ascontiguousarray(frame_seg, np.uint32)
+    out_off = np.ascontiguousarray(out_off, np.uint64)
+    nf = int(first[n]) if n >= 0 else 0
+    if seg.size < nf:
+        raise ValueError(f"{what} frame_seg: {seg.size} entries for {nf} frames")
+    if out_off.size < nf + 1:
+        raise ValueError(f"{what} out_off: {out_off.size} entries for {nf} frames")
+    if n > 0 and data.size < int(data_off[n]):
+        raise ValueError(f"{what} data: {data.size} B given, data_off ends at {int(data_off[n])}")
+    if oo is not None and n > 0 and ob.size < int(oo[n]):
+        raise ValueError(f"{what} opts: {ob.size} B given, opt_off ends at {int(oo[n])}")
+    if out is None:
+        out = np.zeros(int(out_off[nf]), np.uint8)
+    if not isinstance(out, np.ndarray) or out.dtype != np.uint8 or not out.flags.c_contiguous:
+        raise ValueError(f"{what} out: needs a C-contiguous uint8 array")
+    if out.size < int(out_off[nf]):
+        raise ValueError(f"{what} out: {out.size} B given, out_off ends at {int(out_off[nf])}")
+    raw = np.empty(nf, np.uint16) if want_raw else None
+    ipsoa = IpHdrSoA(*[_np_ptr(ipc.get(k)) for k in IP_FIELDS])
+    soa = TcpHdrSoA(*[_np_ptr(cols.get(k)) for k, _ in BUILD_FIELDS])
+    fn = getattr(lib(), f"nsx_tso_ipv{ipver}_tcp_build_host_tuned")
+    _check(fn(ctypes.byref(ipsoa), ctypes.byref(soa), _np_ptr(ob), _np_ptr(oo), _np_ptr(data), _np_ptr(data_off),
+              _np_ptr(mss), n, _np_ptr(first), _np_ptr(seg), nf, _np_ptr(out), _np_ptr(out_off), _np_ptr(raw), num_gpus,
+              _tune(tune)), f"nsx_{what}")
+    return out, raw
+
+
+def tso_ipv4_tcp_build_host(ip: dict, fields: dict, data: np.ndarray, data_off: np.ndarray, mss: np.ndarray,
+                            frame_first: np.ndarray | None = None, frame_seg: np.ndarray | None = None,
+                            out_off: np.ndarray | None = None, opts: np.ndarray | None = None,
+                            opt_off: np.ndarray | None = None, out: np.ndarray | None = None, want_raw: bool = True,
+                            num_gpus: int = 0, tune=None):
+    """Segmentation offload over host-resident super-segments (nsx_tso_ipv4_tcp_build_host): host arrays, one entry
+    per super-segment; the frame map defaults to tso_count_host / tso_layout_host. Returns (out, raw or None), raw
+    holding one sum per frame."""
+    return _tso_build_host(4, ip, fields, data, data_off, mss, frame_first, frame_seg, out_off, opts, opt_off, out,
+                           want_raw, num_gpus, tune)
+
+
+def tso_ipv6_tcp_build_host(ip: dict, fields: dict, data: np.ndarray, data_off: np.ndarray, mss: np.ndarray,
+                            frame_first: np.ndarray | None = None, frame_seg: np.ndarray | None = None,
+                            out_off: np.ndarray | None = None, opts: np.ndarray | None = None,
+                            opt_off: np.ndarray | None = None, out: np.ndarray | None = None, want_raw: bool = True,
+                            num_gpus: int = 0, tune=None):
+    return _tso_build_host(6, ip, fields, data, data_off, mss, frame_first, frame_seg, out_off, opts, opt_off, out,
+                           want_raw, num_gpus, tune)
 
 
 def fill_splitmix64_dev(buf, seed: int, byte_off: int = 0, stream=None):
