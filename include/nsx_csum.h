@@ -383,6 +383,113 @@ int nsx_rx_ipv4_tcp_verify_dev(const void* d_base, const uint64_t* d_offsets, ui
 int nsx_rx_ipv6_tcp_verify_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n, uint64_t* d_mask,
                                uint16_t* d_tcp_raw, nsx_stream_t stream);
 
+/* TCP receive coalescing (GRO), the inverse of segmentation offload: the frames
+ * of a receive batch in, super-segments out — per run of consecutive in-order
+ * frames of one connection one set of header fields, one option block and one
+ * contiguous payload run, in exactly the arrays nsx_tso_ipv4_tcp_build_dev /
+ * nsx_tso_ipv6_tcp_build_dev take. Input as the receive pass: d_base, d_offsets
+ * (n + 1), n, and d_valid, that pass's bitmask over the same frames (required).
+ *
+ * Member. Frame i is a member iff its d_valid bit is set, it is well-formed as
+ * the receive pass of its IP version defines (the length, version, protocol and
+ * fragment conditions above — re-checked here, so a wrong mask never makes the
+ * kernels read outside the frame's own byte range, nor a frame whose bit is
+ * clear at all), and its TCP data offset doff (high nibble of byte 12) has
+ * 5 <= doff and doff*4 <= TCP segment length, which the receive pass does not
+ * check. A non-member belongs to no super-segment and breaks runs. For a member:
+ * pay_i = segment length - doff*4; c_i = the control byte (byte 13); its option
+ * bytes are segment bytes [20, doff*4) verbatim, padding included (a multiple
+ * of 4 bytes).
+ *
+ * same(i, i-1), purely pairwise, holds iff both frames are members; src, dst and
+ * TTL / hop limit are equal; IPv4: both have IHL 5, equal TOS, equal bytes 6-7,
+ * and ident_i == ident_{i-1} + 1 mod 2^16; IPv6: the first 4 header bytes
+ * (version, class, flow) are equal; the TCP ports, ack, window and urgent
+ * pointer are equal; byte 12 is equal and the option bytes are identical;
+ * seq_i == seq_{i-1} + pay_{i-1} mod 2^32; c_{i-1} & (FIN|SYN|RST|PSH|URG) == 0;
+ * c_i & (SYN|RST|URG|CWR) == 0; and (c_i ^ c_{i-1}) & ~(FIN|PSH|CWR) == 0.
+ *
+ * join(i) — frame i continues frame i-1's super-segment — holds iff
+ * same(i, i-1), 1 <= pay_i <= pay_{i-1}, and NOT (i >= 2 and same(i-1, i-2) and
+ * pay_{i-1} < pay_{i-2}). The last clause is a three-frame window, not a
+ * recursion: frame i-1 was itself a short tail. Every frame of a run but the
+ * last therefore carries the same payload length; strictly decreasing runs lose
+ * a few merges (1000, 800, 600, 400, 200 gives [1000, 800], [600], [400],
+ * [200]). A member that does not join is a head. Super-segments are numbered in
+ * frame order; n_super = the number of heads.
+ *
+ * Coalescing is by adjacency only: callers deliver a flow's frames in arrival
+ * order per queue; there is no flow table for interleaved flows. A super-segment
+ * has no IP length field, so there is no 64 KiB cap on it.
+ *
+ * Every member of nsx_gro_out is a writable device array and required. For
+ * super-segment s with first frame f and last frame l, all written:
+ *   src, dst, ident (IPv4; 0 for IPv6), ttl, tclass (IPv4: the TOS byte), flow
+ *     (IPv6; 0 for IPv4) from f — n x 4 (IPv4) or n x 16 (IPv6) address bytes;
+ *   src_port, dst_port, seq_num, ack_num, window, urgent_ptr and offset (the
+ *     whole byte 12) from f; control = c_f | (c_l & (FIN|PSH));
+ *   mss[s] = max(pay_f, 1);
+ *   opts[opt_off[s], opt_off[s+1]) = f's option bytes;
+ *   data[data_off[s], data_off[s+1]) = the payloads of f..l back to back;
+ *   first_frame[s] = f; frame_cnt[s] = l - f + 1.
+ * opt_off[0] = data_off[0] = 0 and both are packed without gaps (n_super + 1
+ * entries). frame_seg[i] = frame i's super-segment, 0xFFFFFFFF for a non-member.
+ * *n_super is a uint64_t in device memory. Per-super-segment entries at index
+ * >= n_super, offset entries past n_super, and data / opts bytes past the last
+ * offset are left exactly as they were. Worst-case extents: n entries per
+ * array, n + 1 offsets, d_offsets[n] - d_offsets[0] data bytes, 40*n option
+ * bytes.
+ *
+ * The defining property: for frames the transmit pass can express (IPv4 with
+ * IHL 5, DF set, MF clear and TOS 0; any IPv6 frame with Next Header 6), the
+ * output arrays go straight into nsx_tso_ipv4_tcp_build_dev /
+ * nsx_tso_ipv6_tcp_build_dev (frame_first = the prefix sum of frame_cnt) and
+ * rebuild every member frame byte for byte. What nsx_ip_hdr_soa cannot carry is
+ * lost: IPv4 options (such a frame is a singleton, its options dropped), a
+ * clear DF bit and a nonzero TOS (kept in tclass, which the IPv4 transmit pass
+ * ignores).
+ *
+ * nsx_gro_work_bytes gives the scratch one call over n frames needs; d_work is
+ * device memory of at least that many bytes, free for reuse once the stream has
+ * run the call. NSX_EINVAL, checked before any launch: a NULL pointer or
+ * member (d_base and d_valid may be NULL when n == 0), n >= 2^32 - 1,
+ * work_bytes too small. Then NSX_ENODEV without a GPU.
+ * n == 0 writes *n_super = 0 and opt_off[0] = data_off[0] = 0, on the stream like
+ * everything else. No allocation, no host sync, no per-stream counters: the
+ * calls can be captured into a graph. There are no _host forms and no
+ * multi-GPU sharding (a run would straddle a shard boundary). */
+typedef struct {
+    uint64_t* n_super;
+    uint8_t*  src;          /* nsx_ip_hdr_soa members */
+    uint8_t*  dst;
+    uint16_t* ident;
+    uint8_t*  ttl;
+    uint8_t*  tclass;
+    uint32_t* flow;
+    uint16_t* src_port;     /* nsx_tcp_hdr_soa members */
+    uint16_t* dst_port;
+    uint32_t* seq_num;
+    uint32_t* ack_num;
+    uint8_t*  offset;
+    uint8_t*  control;
+    uint16_t* window;
+    uint16_t* urgent_ptr;
+    uint32_t* mss;
+    uint8_t*  opts;
+    uint64_t* opt_off;
+    uint8_t*  data;
+    uint64_t* data_off;
+    uint64_t* first_frame;
+    uint32_t* frame_cnt;
+    uint32_t* frame_seg;    /* per frame */
+} nsx_gro_out;
+
+int nsx_gro_work_bytes(uint64_t n, uint64_t* out);
+int nsx_gro_ipv4_tcp_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n, const uint64_t* d_valid,
+                         const nsx_gro_out* out, void* d_work, uint64_t work_bytes, nsx_stream_t stream);
+int nsx_gro_ipv6_tcp_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n, const uint64_t* d_valid,
+                         const nsx_gro_out* out, void* d_work, uint64_t work_bytes, nsx_stream_t stream);
+
 /* ----------------------------------------------------------------------------
  * Host-resident batches: pinned staging, H2D → kernel → D2H double-buffered
  * over two streams per GPU, segments sharded contiguously across num_gpus

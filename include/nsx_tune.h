@@ -138,5 +138,7 @@ int nsx_deal_sets_in_use(uint32_t* out_count);
 /* The _tuned twins of the fused transmit pass (nsx_tx_*): declared in a header of their own, which this one
  * brings in. */
 #include "nsx_tx_tune.h"
+/* ... and of receive coalescing (nsx_gro_*). */
+#include "nsx_gro_tune.h"
 
 #endif /* NSX_TUNE_H */

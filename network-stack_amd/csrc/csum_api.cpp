@@ -470,6 +470,48 @@ NSX_TSO_DEV(4)
 NSX_TSO_DEV(6)
 #undef NSX_TSO_DEV
 
+// ---- receive coalescing: everything validated on the host, then the five launches of gro_kernels.hip ----
+int nsx_gro_work_bytes(uint64_t n, uint64_t* out) {
+    if (!out || n >= 0xFFFFFFFFull) return NSX_EINVAL;
+    *out = nsx::gro_work_bytes(n);
+    return NSX_OK;
+}
+
+static int gro_dev(int ipver, const void* d_base, const uint64_t* d_offsets, uint64_t n, const uint64_t* d_valid,
+                   const nsx_gro_out* o, void* d_work, uint64_t work_bytes, nsx_stream_t stream,
+                   const nsx_tune* tune) {
+    // an empty batch has no frame bytes and no mask words
+    if ((n && (!d_base || !d_valid)) || !d_offsets || !d_work || !o || n >= 0xFFFFFFFFull) return NSX_EINVAL;
+    if (!o->n_super || !o->src || !o->dst || !o->ident || !o->ttl || !o->tclass || !o->flow || !o->src_port ||
+        !o->dst_port || !o->seq_num || !o->ack_num || !o->offset || !o->control || !o->window || !o->urgent_ptr ||
+        !o->mss || !o->opts || !o->opt_off || !o->data || !o->data_off || !o->first_frame || !o->frame_cnt ||
+        !o->frame_seg)
+        return NSX_EINVAL;
+    if (work_bytes < nsx::gro_work_bytes(n)) return NSX_EINVAL;
+    const int dev = current_device();
+    if (dev < 0) return NSX_ENODEV;
+    const nsx::GroOut g{o->n_super, o->src,      o->dst,         o->ident,     o->ttl,     o->tclass,
+                        o->flow,    o->src_port, o->dst_port,    o->seq_num,   o->ack_num, o->offset,
+                        o->control, o->window,   o->urgent_ptr,  o->mss,       o->opts,    o->opt_off,
+                        o->data,    o->data_off, o->first_frame, o->frame_cnt, o->frame_seg};
+    return map_err(nsx::launch_gro(make_cfg(dev, tune), ipver, d_base, d_offsets, n, d_valid, g, d_work,
+                                   static_cast<hipStream_t>(stream)));
+}
+
+#define NSX_GRO_DEV(V)                                                                                             \
+    int nsx_gro_ipv##V##_tcp_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n, const uint64_t* d_valid, \
+                                 const nsx_gro_out* out, void* d_work, uint64_t work_bytes, nsx_stream_t stream) {  \
+        return gro_dev(V, d_base, d_offsets, n, d_valid, out, d_work, work_bytes, stream, nullptr);                \
+    }                                                                                                              \
+    int nsx_gro_ipv##V##_tcp_dev_tuned(const void* d_base, const uint64_t* d_offsets, uint64_t n,                   \
+                                       const uint64_t* d_valid, const nsx_gro_out* out, void* d_work,              \
+                                       uint64_t work_bytes, nsx_stream_t stream, const nsx_tune* tune) {           \
+        return gro_dev(V, d_base, d_offsets, n, d_valid, out, d_work, work_bytes, stream, tune);                   \
+    }
+NSX_GRO_DEV(4)
+NSX_GRO_DEV(6)
+#undef NSX_GRO_DEV
+
 int nsx_tcp_parse_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n, const nsx_tcp_parsed_soa* out,
                       nsx_stream_t stream) {
     if (n == 0) return NSX_OK;

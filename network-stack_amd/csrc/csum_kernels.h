@@ -1,5 +1,5 @@
 // csum_kernels.h — internal launcher interface between the C ABI (csum_api.cpp,
-// host_batch.cpp) and the gfx950 kernels (csum_kernels.hip). Not a public header.
+// host_batch.cpp) and the gfx950 kernels (csum_kernels.hip, gro_kernels.hip). Not a public header.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -86,6 +86,39 @@ hipError_t launch_tso_build(const LaunchCfg& c, int ipver, const IpHdrSoA& ip, c
                             const uint8_t* opts, const uint64_t* opt_off, const uint8_t* data,
                             const uint64_t* data_off, uint64_t data_bytes, uint64_t n_frames, uint8_t* out,
                             const uint64_t* out_off, uint16_t* raw, hipStream_t st);
+// Receive coalescing (nsx_gro_*, gro_kernels.hip): the writable device arrays of include/nsx_csum.h nsx_gro_out,
+// member for member.
+struct GroOut {
+    uint64_t* n_super;
+    uint8_t* src;
+    uint8_t* dst;
+    uint16_t* ident;
+    uint8_t* ttl;
+    uint8_t* tclass;
+    uint32_t* flow;
+    uint16_t* src_port;
+    uint16_t* dst_port;
+    uint32_t* seq_num;
+    uint32_t* ack_num;
+    uint8_t* offset;
+    uint8_t* control;
+    uint16_t* window;
+    uint16_t* urgent_ptr;
+    uint32_t* mss;
+    uint8_t* opts;
+    uint64_t* opt_off;
+    uint8_t* data;
+    uint64_t* data_off;
+    uint64_t* first_frame;
+    uint32_t* frame_cnt;
+    uint32_t* frame_seg;
+};
+// Scratch bytes of one launch_gro over n frames (whatever the tune).
+uint64_t gro_work_bytes(uint64_t n);
+// Frames → super-segments (ipver 4 / 6); n < 2^32 - 1, work of at least gro_work_bytes(n). c.run_segs = frames per
+// scan block (0 = 4096, clamped to 16..65536), c.blocks_per_cu = the copy kernel's grid (default 8).
+hipError_t launch_gro(const LaunchCfg& c, int ipver, const void* d_base, const uint64_t* d_offsets, uint64_t n,
+                      const uint64_t* valid, const GroOut& o, void* work, hipStream_t st);
 struct TcpParsedSoA {  // device arrays, one entry per segment; every member nullable
     uint16_t* src_port;
     uint16_t* dst_port;

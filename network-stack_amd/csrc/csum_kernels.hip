@@ -33,18 +33,11 @@
 #include <vector>
 
 #include "csum_kernels.h"
+// kWave / kRow / kBlock, u32x4, keep_mask, kOOB, make_rsrc, bld16, readlane64, keep_bytes, bperm, realign
+#include "kernel_util.h"
 
 namespace nsx {
 namespace {
-
-constexpr uint32_t kWave = 64;
-constexpr uint32_t kRow = 1024;        // bytes per wave-wide 16 B/lane load
-constexpr uint32_t kBlock = 256;       // 4 waves
-constexpr uint32_t kWavesPerBlock = kBlock / kWave;
-
-// 16 bytes at a 4-byte-aligned address: hipcc emits one global_load_dwordx4
-// (gfx950 serves dword-aligned multi-dword global loads in hardware).
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4), aligned(4)));
 
 template <bool NT>
 __device__ __forceinline__ u32x4 ld16(const uint8_t* p) {
@@ -198,16 +191,6 @@ __device__ __forceinline__ ChunkDeal chunk_deal(TaskIter& it, uint32_t wave, uin
 // num_records ending at the 4-aligned end of the batch, a 16-byte load that
 // straddles the end returns exactly its in-range dwords, so no tail path.
 // ---------------------------------------------------------------------------
-// Mask for the chunk of lane byte offset ql inside a row whose segment bytes are
-// [lo_r, hi_r) relative to the row start (both clamped, 32-bit).
-__device__ __forceinline__ uint32_t keep_mask(int32_t lo_r, int32_t hi_r, int32_t d) {
-    const int32_t e = min(max(hi_r - d, 0), 4), s = min(max(lo_r - d, 0), 4);
-    const uint32_t me = e >= 4 ? 0xFFFFFFFFu : ((1u << (8 * e)) - 1u);
-    const uint32_t ms = s >= 4 ? 0xFFFFFFFFu : ((1u << (8 * s)) - 1u);
-    return me & ~ms;
-}
-
-constexpr uint32_t kOOB = 0x80000000u;  // voffset that is always out of range (num_records < 2^31)
 // s_waitcnt operand (gfx9 encoding): vmcnt(0), expcnt and lgkmcnt left at their maxima (no wait)
 constexpr int kWaitVm0 = 0x0F70;
 // Cache-policy operand of a buffer store on gfx950: sc1 (bit 4) = write-through, the line leaves the XCD's L2.
@@ -246,20 +229,6 @@ constexpr uint32_t kDealPoolShift = NSX_DEAL_POOL_SHIFT;
 constexpr uint32_t kDealHeads = NSX_DEAL_HEADS;
 constexpr uint32_t kDealStride = 16;
 constexpr uint32_t kDealSlots = 64;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, uint64_t bytes) {
-    // Wave-uniform inputs only, so no waterfall loop (guide T20); clamp without a
-    // 64-bit unsigned compare (SALU has none: hipcc would borrow VGPRs for it).
-    const uint32_t nr = (bytes >> 31) ? kOOB - 1 : (uint32_t)bytes;
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)nr, 0x00020000);
-}
-
-template <bool NT>
-__device__ __forceinline__ u32x4 bld16(__amdgpu_buffer_rsrc_t r, uint32_t voff) {
-    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-    v4u x = __builtin_amdgcn_raw_buffer_load_b128(r, voff, 0, NT ? 2 : 0);
-    return u32x4{x.x, x.y, x.z, x.w};
-}
 
 // Byte mask keeping the low `keep` bytes of a dword (keep in 1..3).
 __device__ __forceinline__ uint32_t low_keep(uint32_t keep) { return (1u << (8 * keep)) - 1u; }
@@ -561,12 +530,6 @@ __global__ __launch_bounds__(kBlock) void csum_block_kernel(
     }
 }
 
-__device__ __forceinline__ uint64_t readlane64(uint64_t v, uint32_t k) {
-    const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)v, k);
-    const uint32_t hi = __builtin_amdgcn_readlane((uint32_t)(v >> 32), k);
-    return ((uint64_t)hi << 32) | lo;
-}
-
 // ---------------------------------------------------------------------------
 // Ragged prefix-scan kernel (the default ragged kernel).
 //
@@ -588,15 +551,6 @@ __device__ __forceinline__ uint64_t readlane64(uint64_t v, uint32_t k) {
 // ---------------------------------------------------------------------------
 constexpr uint32_t kScanRun = 63;
 
-// Keep bytes [lo, hi) (0 ≤ lo ≤ hi ≤ 16) of a 16-byte chunk.
-__device__ __forceinline__ u32x4 keep_bytes(u32x4 x, int32_t lo, int32_t hi) {
-    x.x &= keep_mask(lo, hi, 0);
-    x.y &= keep_mask(lo, hi, 4);
-    x.z &= keep_mask(lo, hi, 8);
-    x.w &= keep_mask(lo, hi, 12);
-    return x;
-}
-
 // Inclusive prefix sum over the 64 lanes (DPP row shifts, then row broadcasts).
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
     v += __builtin_amdgcn_update_dpp(0u, v, 0x111, 0xF, 0xF, false);  // row_shr:1
@@ -606,10 +560,6 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
     v += __builtin_amdgcn_update_dpp(0u, v, 0x142, 0xA, 0xF, false);  // row_bcast:15
     v += __builtin_amdgcn_update_dpp(0u, v, 0x143, 0xC, 0xF, false);  // row_bcast:31
     return v;
-}
-
-__device__ __forceinline__ uint32_t bperm(uint32_t v, uint32_t src_lane) {
-    return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(src_lane * 4), (int)v);
 }
 
 __device__ __forceinline__ uint64_t ld_off(__amdgpu_buffer_rsrc_t ofs, uint32_t i) {
@@ -2413,11 +2363,6 @@ __device__ __forceinline__ uint32_t bswap32u(uint32_t v) {
 // chunk needs no mask or branch. Dword 4 (urgent pointer + checksum field) is
 // written once, last, with the field.
 constexpr uint32_t kBuildRows = 2;
-
-__device__ __forceinline__ u32x4 realign(u32x4 lo, uint32_t hi, uint32_t sh) {
-    return u32x4{__builtin_amdgcn_alignbyte(lo.y, lo.x, sh), __builtin_amdgcn_alignbyte(lo.z, lo.y, sh),
-                 __builtin_amdgcn_alignbyte(lo.w, lo.z, sh), __builtin_amdgcn_alignbyte(hi, lo.w, sh)};
-}
 
 struct BuildSeg {  // wave-uniform description of one segment
     uint32_t D0, D1, D2, D3, D4;  // header dwords as stored (LE view), field = 0

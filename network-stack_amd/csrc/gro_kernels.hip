@@ -1,0 +1,546 @@
+// gro_kernels.hip — gfx950 kernels of TCP receive coalescing (nsx_gro_ipv4_tcp_dev / nsx_gro_ipv6_tcp_dev,
+// include/nsx_csum.h): the inverse of segmentation offload. Runs of consecutive in-order frames of one connection
+// become super-segments in the SoA format nsx_tso_*_build_dev takes.
+//
+// Five launches, none of which waits on another workgroup:
+//   head   per frame: member, same(i, i-1), payload / option / header lengths → one meta dword in the workspace.
+//          A wave owns 63 consecutive frames plus the frame before them in lane 0, so every header is fetched by
+//          one lane and the neighbour's fields come by ds_bpermute.
+//   reduce per scan block: the number of heads, their option bytes, the payload bytes.
+//   scan   one workgroup: exclusive prefix sums of the block sums; writes n_super and the closing offsets.
+//   apply  per scan block: frame_seg, each frame's payload destination, and at heads first_frame / opt_off /
+//          data_off; the last frame of each run goes to the workspace.
+//   emit   the hot path. A wave takes a group of consecutive frames and copies each payload to its destination
+//          offset: 16-byte loads through a descriptor clamped to the frame, realigned by the (source −
+//          destination) byte shift, 16-byte stores at destination-aligned addresses, byte / short / dword stores
+//          at the two ends (two frames' payloads may meet inside one dword, so nothing is read back). The lane
+//          that owns a head frame also writes the super-segment's fields and option bytes.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "csum_kernels.h"
+#include "kernel_util.h"
+
+namespace nsx {
+namespace {
+
+// meta dword of a frame (0 for a non-member): payload bytes, option dwords, bytes from the frame's start to its
+// payload (IP header + doff*4 ≤ 60 + 60), same(i, i-1), member
+constexpr uint32_t kPayMask = 0xFFFFu;
+constexpr uint32_t kOptShift = 16, kHdrShift = 20;
+constexpr uint32_t kSame = 1u << 28, kMember = 1u << 29;
+constexpr uint32_t kHeadFrames = 63;   // frames per wave of the head pass (lane 0 holds the frame before them)
+constexpr uint32_t kEmitGroup = 16;    // frames per wave task of the emit pass
+constexpr uint32_t kScanBlockDefault = 4096, kScanBlockMin = 16, kScanBlockMax = 65536;
+
+__device__ __forceinline__ uint32_t m_pay(uint32_t m) { return m & kPayMask; }
+__device__ __forceinline__ uint32_t m_optb(uint32_t m) { return ((m >> kOptShift) & 15u) * 4u; }
+__device__ __forceinline__ uint32_t m_hdr(uint32_t m) { return (m >> kHdrShift) & 127u; }
+
+// join(i) from the meta dwords of frames i, i-1 and i-2 (0 where there is no such frame): the three-frame window
+// of include/nsx_csum.h.
+__device__ __forceinline__ bool gro_join(uint32_t m0, uint32_t m1, uint32_t m2) {
+    const uint32_t p0 = m_pay(m0), p1 = m_pay(m1), p2 = m_pay(m2);
+    return (m0 & kSame) && p0 >= 1u && p0 <= p1 && !((m1 & kSame) && p1 < p2);
+}
+
+__device__ __forceinline__ uint32_t bswap16(uint32_t v) { return ((v & 0xFFu) << 8) | ((v >> 8) & 0xFFu); }
+__device__ __forceinline__ uint32_t bswap32(uint32_t v) { return __builtin_bswap32(v); }
+
+// A frame's bytes as dwords: the window starts at the frame's address rounded down to 4 bytes; a dword that
+// holds no byte of the frame is not loaded and reads 0 (an aligned dword holding a readable byte never crosses a
+// page). at(b): the little-endian dword at frame byte b (a multiple of 4).
+struct FrameWin {
+    const uint32_t* w;
+    uint32_t sh, end;  // frame start inside the first dword; window bytes up to the frame's end
+    __device__ __forceinline__ uint32_t word(uint32_t k) const { return 4u * k < end ? w[k] : 0u; }
+    __device__ __forceinline__ uint32_t at(uint32_t b) const {
+        const uint32_t k = b >> 2;
+        return __builtin_amdgcn_alignbyte(word(k + 1), word(k), sh);
+    }
+};
+
+__device__ __forceinline__ FrameWin frame_win(const uint8_t* p, uint32_t flen) {
+    const uint32_t sh = (uint32_t)((uintptr_t)p & 3u);
+    return FrameWin{reinterpret_cast<const uint32_t*>(p - sh), sh, flen ? sh + flen : 0u};
+}
+
+// ------------------------------------------------------------------------------------------------ head pass
+template <bool V6>
+__global__ __launch_bounds__(kBlock) void gro_head_kernel(const uint8_t* __restrict__ base,
+                                                          const uint64_t* __restrict__ offsets, uint32_t n,
+                                                          const uint64_t* __restrict__ valid,
+                                                          uint32_t* __restrict__ meta) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t wave = (uint64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
+    const uint64_t first = wave * kHeadFrames;  // lane 1's frame
+    if (first >= n) return;                     // wave-uniform
+    const int64_t fi = (int64_t)first + lane - 1;
+    const bool live = fi >= 0 && fi < (int64_t)n;
+    const uint32_t i = live ? (uint32_t)fi : 0u;
+    const uint64_t o0 = live ? offsets[i] : 0u, o1 = live ? offsets[(uint64_t)i + 1] : 0u;
+    // a frame longer than any length field can say is no member; the cap keeps the window arithmetic in 32 bits
+    const uint32_t flen = live ? (uint32_t)min(o1 - o0, (uint64_t)0x20000u) : 0u;
+    const bool vbit = live && ((valid[i >> 6] >> (i & 63u)) & 1u);
+    const FrameWin F = frame_win(base + o0, vbit ? flen : 0u);  // a frame the mask rejects is not read at all
+
+    constexpr int NK = V6 ? 10 : 4;  // IP words that must be equal
+    uint32_t K[NK];
+    uint32_t iph, seg, ident = 0;
+    bool ok;
+    if constexpr (V6) {
+        const uint32_t h0 = F.at(0), h1 = F.at(4);
+        iph = 40u;
+        ok = flen >= 60u && (h0 & 0xF0u) == 0x60u && 40u + bswap16(h1) == flen && ((h1 >> 16) & 0xFFu) == 6u;
+        seg = flen - 40u;
+        K[0] = h0;         // version, class, flow
+        K[1] = h1 >> 24;   // hop limit
+#pragma unroll
+        for (int k = 0; k < 8; ++k) K[2 + k] = F.at(8 + 4 * k);
+    } else {
+        const uint32_t h0 = F.at(0), h1 = F.at(4), h2 = F.at(8);
+        iph = (h0 & 15u) * 4u;
+        ok = flen >= 40u && (h0 & 0xF0u) == 0x40u && iph >= 20u && iph <= flen && bswap16(h0 >> 16) == flen &&
+             (h1 & 0xFF3F0000u) == 0u && ((h2 >> 8) & 0xFFu) == 6u && flen - iph >= 20u;
+        seg = flen - iph;
+        ident = bswap16(h1);
+        // IHL 5 is a condition of same(), not of membership: a frame with IP options is a singleton
+        K[0] = (h0 & 0xFFFFu) | (h1 & 0xFFFF0000u);  // version / IHL, TOS, bytes 6-7
+        K[1] = h2 & 0xFFu;                           // TTL
+        K[2] = F.at(12);
+        K[3] = F.at(16);
+    }
+    ok = ok && vbit;
+    if (!ok) iph = 0u;
+    uint32_t T[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) T[k] = ok ? F.at(iph + 4u * k) : 0u;
+    const uint32_t doff = (T[3] >> 4) & 15u;
+    const bool member = ok && doff >= 5u && doff * 4u <= seg;
+    const uint32_t optdw = member ? doff - 5u : 0u;
+    const uint32_t pay = member ? seg - doff * 4u : 0u;
+    uint32_t O[10];
+#pragma unroll
+    for (int k = 0; k < 10; ++k) O[k] = (uint32_t)k < optdw ? F.at(iph + 20u + 4u * k) : 0u;
+    const uint32_t ctl = (T[3] >> 8) & 0xFFu;
+    const uint32_t seq = bswap32(T[1]);
+
+    // the frame before: lane - 1 (lane 0's own result is not used)
+    const uint32_t src = (lane + 63u) & 63u;
+    // (every ds_bpermute runs with the whole wave active: nothing below is skipped for a lane)
+    const uint32_t pmember = bperm(member ? 1u : 0u, src);
+    bool same = member && pmember != 0u;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) same = (bperm(K[k], src) == K[k]) && same;
+    if constexpr (!V6) {
+        same = (((bperm(ident, src) + 1u) & 0xFFFFu) == ident) && same;
+        same = same && iph == 20u;  // the previous frame's IHL is equal (K[0])
+    }
+    same = (bperm(T[0], src) == T[0]) && same;                              // ports
+    same = (bperm(seq + pay, src) == seq) && same;                          // in order
+    same = (bperm(T[2], src) == T[2]) && same;                              // ack
+    same = (((bperm(T[3], src) ^ T[3]) & 0xFFFF00FFu) == 0u) && same;       // byte 12, window
+    same = (((bperm(T[4], src) ^ T[4]) & 0xFFFF0000u) == 0u) && same;       // urgent pointer
+#pragma unroll
+    for (int k = 0; k < 10; ++k) same = (bperm(O[k], src) == O[k]) && same;
+    const uint32_t pctl = bperm(ctl, src);
+    same = same && (pctl & 0x2Fu) == 0u && (ctl & 0xA6u) == 0u && ((ctl ^ pctl) & 0x76u) == 0u;
+
+    if (live && lane >= 1u)
+        meta[i] = member ? pay | (optdw << kOptShift) | ((iph + doff * 4u) << kHdrShift) | (same ? kSame : 0u) | kMember
+                         : 0u;
+}
+
+// ------------------------------------------------------------------------------------------------ scan
+// Exclusive prefix sums over the 256 threads of a block, K values at once; total[] = the block's sums.
+template <int K>
+__device__ __forceinline__ void block_excl_scan(uint64_t (&v)[K], uint64_t (&total)[K], uint64_t (*lds)[K]) {
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    uint64_t incl[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        uint64_t x = v[k];
+        for (uint32_t d = 1; d < 64u; d <<= 1) {
+            const uint64_t y = __shfl_up((unsigned long long)x, d, 64);
+            if (lane >= d) x += y;
+        }
+        incl[k] = x;
+        if (lane == 63u) lds[w][k] = x;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        uint64_t pre = 0, tot = 0;
+        for (uint32_t j = 0; j < kWavesPerBlock; ++j) {
+            const uint64_t s = lds[j][k];
+            if (j < w) pre += s;
+            tot += s;
+        }
+        total[k] = tot;
+        v[k] = incl[k] - v[k] + pre;
+    }
+    __syncthreads();
+}
+
+struct GroFrame {
+    uint32_t m, head, last;  // meta; a head; the last frame of its run
+};
+
+__device__ __forceinline__ GroFrame gro_frame(const uint32_t* __restrict__ meta, uint32_t i, uint32_t n, bool live,
+                                              bool want_last) {
+    GroFrame f{0u, 0u, 0u};
+    if (!live) return f;
+    const uint32_t m0 = meta[i], m1 = i >= 1u ? meta[i - 1u] : 0u, m2 = i >= 2u ? meta[i - 2u] : 0u;
+    f.m = m0;
+    f.head = (m0 & kMember) && !gro_join(m0, m1, m2);
+    if (want_last && (m0 & kMember)) f.last = i + 1u == n || !gro_join(meta[i + 1u], m0, m1);
+    return f;
+}
+
+// APPLY false: sums[3b..] = the block's (heads, option bytes of heads, payload bytes). APPLY true: sums holds the
+// exclusive prefix of those over the blocks, and the per-frame and per-head outputs are written.
+template <bool APPLY>
+__global__ __launch_bounds__(kBlock) void gro_scan_block_kernel(const uint32_t* __restrict__ meta, uint32_t n,
+                                                                uint32_t per_block, uint64_t* __restrict__ sums,
+                                                                uint64_t* __restrict__ wdst,
+                                                                uint32_t* __restrict__ wlast, GroOut o) {
+    __shared__ uint64_t lds[kWavesPerBlock][3];
+    const uint64_t lo = (uint64_t)blockIdx.x * per_block, hi = min(lo + per_block, (uint64_t)n);
+    uint64_t carry[3] = {0, 0, 0};
+    if (APPLY) {
+        carry[0] = sums[3u * blockIdx.x];
+        carry[1] = sums[3u * blockIdx.x + 1u];
+        carry[2] = sums[3u * blockIdx.x + 2u];
+    }
+    for (uint64_t t = lo; t < hi; t += kBlock) {  // block-uniform trip count
+        const uint64_t fi = t + threadIdx.x;
+        const bool live = fi < hi;
+        const uint32_t i = (uint32_t)fi;
+        const GroFrame f = gro_frame(meta, i, n, live, APPLY);
+        uint64_t v[3] = {f.head, f.head ? m_optb(f.m) : 0u, m_pay(f.m)}, tot[3];
+        block_excl_scan<3>(v, tot, lds);
+        if (APPLY && live) {
+            const bool member = f.m & kMember;
+            const uint32_t s = (uint32_t)(carry[0] + v[0]) + f.head - 1u;
+            o.frame_seg[i] = member ? s : 0xFFFFFFFFu;
+            wdst[i] = carry[2] + v[2];
+            if (f.head) {
+                o.first_frame[s] = i;
+                o.opt_off[s] = carry[1] + v[1];
+                o.data_off[s] = carry[2] + v[2];
+            }
+            if (f.last) wlast[s] = i;
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) carry[k] += tot[k];
+    }
+    if (!APPLY && threadIdx.x == 0) {
+        sums[3u * blockIdx.x] = carry[0];
+        sums[3u * blockIdx.x + 1u] = carry[1];
+        sums[3u * blockIdx.x + 2u] = carry[2];
+    }
+}
+
+// One workgroup: sums (nb triples) → their exclusive prefix in place; the totals close the outputs.
+__global__ __launch_bounds__(kBlock) void gro_scan_sums_kernel(uint64_t* __restrict__ sums, uint32_t nb, GroOut o) {
+    __shared__ uint64_t lds[kWavesPerBlock][3];
+    uint64_t carry[3] = {0, 0, 0};
+    for (uint32_t t = 0; t < nb; t += kBlock) {
+        const uint32_t b = t + threadIdx.x;
+        const bool live = b < nb;
+        uint64_t v[3], tot[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) v[k] = live ? sums[3u * b + k] : 0u;
+        block_excl_scan<3>(v, tot, lds);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            if (live) sums[3u * b + k] = carry[k] + v[k];
+            carry[k] += tot[k];
+        }
+    }
+    if (threadIdx.x == 0) {
+        *o.n_super = carry[0];
+        if (nb == 0) o.opt_off[0] = o.data_off[0] = 0;  // with frames, entry 0 belongs to the first head (or is the total)
+        o.opt_off[carry[0]] = carry[1];
+        o.data_off[carry[0]] = carry[2];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ emit + copy
+// Bytes [lo, hi) of the 16-byte chunk x to q (16-aligned): whole dwords where the range covers them, else shorts
+// and bytes; nothing outside the range is touched.
+__device__ __forceinline__ void store_edge(uint8_t* q, u32x4 x, int32_t lo, int32_t hi) {
+    const uint32_t d[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int32_t s = min(max(lo - 4 * k, 0), 4), e = min(max(hi - 4 * k, 0), 4);
+        if (s >= e) continue;
+        uint8_t* p = q + 4 * k;
+        if (s == 0 && e == 4) {
+            *reinterpret_cast<uint32_t*>(p) = d[k];
+            continue;
+        }
+        if (s == 0 && e >= 2) {
+            *reinterpret_cast<uint16_t*>(p) = (uint16_t)d[k];
+        } else {
+            if (s == 0) p[0] = (uint8_t)d[k];
+            if (s <= 1 && e > 1) p[1] = (uint8_t)(d[k] >> 8);
+        }
+        if (s <= 2 && e == 4) {
+            *reinterpret_cast<uint16_t*>(p + 2) = (uint16_t)(d[k] >> 16);
+        } else {
+            if (s <= 2 && e > 2) p[2] = (uint8_t)(d[k] >> 16);
+            if (s <= 3 && e > 3) p[3] = (uint8_t)(d[k] >> 24);
+        }
+    }
+}
+
+typedef uint32_t a16x4 __attribute__((ext_vector_type(4)));  // 16-aligned: one global_store_dwordx4
+
+// One frame's payload copy, wave-uniform: destination chunk c is the 16 bytes at q0 + 16c (q0 16-aligned), of
+// which bytes [a, end) from q0 belong to the payload; its source bytes start sh bytes into offset 16c of srs, a
+// descriptor from the 4-aligned address at or below (payload − a) — at least 22 bytes into the frame, whose headers
+// take 40 — to the dword holding the frame's last byte. chunks == 0: no job.
+struct CopyJob {
+    __amdgpu_buffer_rsrc_t srs;
+    uint8_t* q0;
+    uint32_t a, end, sh, chunks;
+};
+
+// The next frame of the group, from k on, that has payload (k moves past it); chunks = 0 when there is none.
+__device__ __forceinline__ CopyJob next_job(const uint8_t* __restrict__ base, uint8_t* data, uint32_t m, uint64_t off,
+                                            uint64_t dst, uint32_t cnt, uint32_t& k) {
+    CopyJob j{make_rsrc(base, 0), data, 0u, 0u, 0u, 0u};
+    while (k < cnt) {
+        const uint32_t mk = __builtin_amdgcn_readlane(m, k);
+        const uint32_t L = m_pay(mk);
+        if (L == 0u) {
+            ++k;
+            continue;
+        }
+        const uint8_t* sp = base + readlane64(off, k) + m_hdr(mk);  // the payload: it ends with the frame
+        uint8_t* dp = data + readlane64(dst, k);
+        ++k;
+        j.a = (uint32_t)((uintptr_t)dp & 15u);
+        j.q0 = dp - j.a;
+        const uint8_t* s0 = sp - j.a;
+        j.sh = (uint32_t)((uintptr_t)s0 & 3u);
+        j.srs = make_rsrc(s0 - j.sh, ((uint64_t)(j.sh + j.a + L) + 3u) & ~3ull);
+        j.end = j.a + L;
+        j.chunks = (j.end + 15u) >> 4;
+        break;
+    }
+    return j;
+}
+
+struct RowPair {
+    u32x4 lo[2];
+    uint32_t hi[2];
+};
+
+// Chunks c0 + lane and c0 + 64 + lane of job j: five source dwords each (the fifth only when the copy shifts).
+__device__ __forceinline__ RowPair load_pair(const CopyJob& j, uint32_t c0, uint32_t lane) {
+    RowPair p;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const uint32_t c = c0 + r * kWave + lane;
+        const bool on = c < j.chunks;
+        p.lo[r] = bld16<true>(j.srs, on ? c * 16u : kOOB);
+        p.hi[r] = __builtin_amdgcn_raw_buffer_load_b32(j.srs, on && j.sh ? c * 16u + 16u : kOOB, 0, 2);
+    }
+    return p;
+}
+
+__device__ __forceinline__ void store_pair(const CopyJob& j, uint32_t c0, uint32_t lane, const RowPair& p) {
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const uint32_t c = c0 + r * kWave + lane;
+        if (c >= j.chunks) continue;
+        const u32x4 x = j.sh ? realign(p.lo[r], p.hi[r], j.sh) : p.lo[r];
+        const int32_t b0 = (int32_t)j.a - (int32_t)(c * 16u), b1 = (int32_t)j.end - (int32_t)(c * 16u);
+        uint8_t* q = j.q0 + (uint64_t)c * 16u;
+        if (b0 <= 0 && b1 >= 16) *reinterpret_cast<a16x4*>(q) = a16x4{x.x, x.y, x.z, x.w};
+        else store_edge(q, x, max(b0, 0), min(b1, 16));
+    }
+}
+
+// The fields and option bytes of the super-segment s whose first frame is i (one lane).
+template <bool V6>
+__device__ __forceinline__ void emit_head(const uint8_t* __restrict__ base, const uint64_t* __restrict__ offsets,
+                                          const uint32_t* __restrict__ meta, const uint32_t* __restrict__ wlast,
+                                          const GroOut& o, uint32_t i, uint32_t s, uint32_t m, uint64_t off) {
+    const uint32_t optb = m_optb(m), hdr = m_hdr(m), pay = m_pay(m);
+    const uint32_t iph = hdr - 20u - optb;
+    const FrameWin F = frame_win(base + off, hdr + pay);
+    if constexpr (V6) {
+        const uint32_t h0 = bswap32(F.at(0));
+        uint32_t* sp = reinterpret_cast<uint32_t*>(o.src) + 4ull * s;  // 16-byte rows of a device allocation
+        uint32_t* dp = reinterpret_cast<uint32_t*>(o.dst) + 4ull * s;
+        const bool al = (((uintptr_t)o.src | (uintptr_t)o.dst) & 3u) == 0u;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t a = F.at(8 + 4 * k), b = F.at(24 + 4 * k);
+            if (al) {
+                sp[k] = a;
+                dp[k] = b;
+            } else {
+                for (int j = 0; j < 4; ++j) {
+                    o.src[16ull * s + 4 * k + j] = (uint8_t)(a >> (8 * j));
+                    o.dst[16ull * s + 4 * k + j] = (uint8_t)(b >> (8 * j));
+                }
+            }
+        }
+        o.ident[s] = 0;
+        o.ttl[s] = (uint8_t)(F.at(4) >> 24);
+        o.tclass[s] = (uint8_t)(h0 >> 20);
+        o.flow[s] = h0 & 0xFFFFFu;
+    } else {
+        const uint32_t h0 = F.at(0), a = F.at(12), b = F.at(16);
+        for (int j = 0; j < 4; ++j) {
+            o.src[4ull * s + j] = (uint8_t)(a >> (8 * j));
+            o.dst[4ull * s + j] = (uint8_t)(b >> (8 * j));
+        }
+        o.ident[s] = (uint16_t)bswap16(F.at(4));
+        o.ttl[s] = (uint8_t)F.at(8);
+        o.tclass[s] = (uint8_t)(h0 >> 8);
+        o.flow[s] = 0;
+    }
+    const uint32_t t0 = F.at(iph), t3 = F.at(iph + 12u);
+    o.src_port[s] = (uint16_t)bswap16(t0);
+    o.dst_port[s] = (uint16_t)bswap16(t0 >> 16);
+    o.seq_num[s] = bswap32(F.at(iph + 4u));
+    o.ack_num[s] = bswap32(F.at(iph + 8u));
+    o.offset[s] = (uint8_t)t3;
+    o.window[s] = (uint16_t)bswap16(t3 >> 16);
+    o.urgent_ptr[s] = (uint16_t)bswap16(F.at(iph + 16u) >> 16);
+    o.mss[s] = max(pay, 1u);
+    const uint32_t l = wlast[s];
+    o.frame_cnt[s] = l - i + 1u;
+    uint32_t ctl = (t3 >> 8) & 0xFFu;
+    if (l != i) {  // FIN / PSH of the run's last frame: its control byte, 13 bytes into its TCP header
+        const uint32_t ml = meta[l];
+        ctl |= base[offsets[l] + (m_hdr(ml) - 20u - m_optb(ml)) + 13u] & 0x09u;
+    }
+    o.control[s] = (uint8_t)ctl;
+    uint8_t* op = o.opts + o.opt_off[s];
+    const bool oal = ((uintptr_t)op & 3u) == 0u;
+    for (uint32_t k = 0; k < optb; k += 4u) {
+        const uint32_t v = F.at(iph + 20u + k);
+        if (oal) {
+            *reinterpret_cast<uint32_t*>(op + k) = v;
+        } else {
+            for (int j = 0; j < 4; ++j) op[k + j] = (uint8_t)(v >> (8 * j));
+        }
+    }
+}
+
+template <bool V6>
+__global__ __launch_bounds__(kBlock) void gro_emit_kernel(const uint8_t* __restrict__ base,
+                                                          const uint64_t* __restrict__ offsets, uint32_t n,
+                                                          const uint32_t* __restrict__ meta,
+                                                          const uint64_t* __restrict__ wdst,
+                                                          const uint32_t* __restrict__ wlast, GroOut o) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t nwaves = (uint64_t)gridDim.x * kWavesPerBlock;
+    const uint64_t groups = ((uint64_t)n + kEmitGroup - 1u) / kEmitGroup;
+    for (uint64_t g = (uint64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6); g < groups; g += nwaves) {
+        const uint32_t g0 = (uint32_t)(g * kEmitGroup), cnt = min(kEmitGroup, n - g0);
+        // lane j < cnt: frame g0 + j
+        const bool own = lane < cnt;
+        const uint32_t i = g0 + (own ? lane : 0u);
+        const uint32_t m = own ? meta[i] : 0u;
+        const uint64_t off = own ? offsets[i] : 0u, dst = own ? wdst[i] : 0u;
+        if (m & kMember) {
+            const uint32_t s = o.frame_seg[i];
+            if (o.first_frame[s] == i) emit_head<V6>(base, offsets, meta, wlast, o, i, s, m, off);
+        }
+        // The group's payloads as one stream of row pairs (2 KiB of destination each), software-pipelined: the
+        // loads of the next pair — of this frame, or the first of the next frame with a payload — are issued
+        // before the current pair is stored. A pair past the group's end loads nothing (every offset out of range).
+        uint32_t k = 0;
+        CopyJob cur = next_job(base, o.data, m, off, dst, cnt, k);
+        uint32_t c0 = 0;
+        RowPair A = load_pair(cur, c0, lane);
+        while (cur.chunks) {  // wave-uniform
+            CopyJob nj = cur;
+            uint32_t nc = c0 + 2u * kWave;
+            if (nc >= cur.chunks) {
+                nj = next_job(base, o.data, m, off, dst, cnt, k);
+                nc = 0;
+            }
+            const RowPair B = load_pair(nj, nc, lane);
+            store_pair(cur, c0, lane, A);
+            cur = nj;
+            c0 = nc;
+            A = B;
+        }
+    }
+}
+
+uint32_t scan_block_frames(const LaunchCfg& c) {
+    if (c.run_segs <= 0) return kScanBlockDefault;
+    return std::min<uint32_t>(std::max<uint32_t>((uint32_t)c.run_segs, kScanBlockMin), kScanBlockMax);
+}
+
+struct GroWork {
+    uint64_t sums, wdst, meta, wlast, total;  // byte offsets from the workspace rounded up to 8
+};
+
+GroWork gro_layout(uint64_t n) {
+    GroWork w;
+    const uint64_t nb_max = (n + kScanBlockMin - 1) / kScanBlockMin;  // the smallest scan block a tune can ask for
+    w.sums = 0;
+    w.wdst = w.sums + 24 * (nb_max + 1);
+    w.meta = w.wdst + 8 * n;
+    w.wlast = w.meta + 4 * n;
+    w.total = w.wlast + 4 * n + 8;  // + the rounding of the caller's pointer
+    return w;
+}
+
+}  // namespace
+
+uint64_t gro_work_bytes(uint64_t n) { return gro_layout(n).total; }
+
+hipError_t launch_gro(const LaunchCfg& c, int ipver, const void* d_base, const uint64_t* d_offsets, uint64_t n64,
+                      const uint64_t* valid, const GroOut& o, void* work, hipStream_t st) {
+    const uint32_t n = (uint32_t)n64;  // n < 2^32 - 1 (csum_api.cpp)
+    const GroWork L = gro_layout(n);
+    uint8_t* w = reinterpret_cast<uint8_t*>(((uintptr_t)work + 7u) & ~(uintptr_t)7u);
+    uint64_t* sums = reinterpret_cast<uint64_t*>(w + L.sums);
+    uint64_t* wdst = reinterpret_cast<uint64_t*>(w + L.wdst);
+    uint32_t* meta = reinterpret_cast<uint32_t*>(w + L.meta);
+    uint32_t* wlast = reinterpret_cast<uint32_t*>(w + L.wlast);
+    const uint8_t* base = static_cast<const uint8_t*>(d_base);
+    const uint32_t per = scan_block_frames(c);
+    const uint32_t nb = (uint32_t)(((uint64_t)n + per - 1) / per);
+    if (n) {
+        const uint64_t hw = ((uint64_t)n + kHeadFrames - 1) / kHeadFrames;
+        const uint32_t hgrid = (uint32_t)((hw + kWavesPerBlock - 1) / kWavesPerBlock);
+        if (ipver == 6)
+            hipLaunchKernelGGL(gro_head_kernel<true>, dim3(hgrid), dim3(kBlock), 0, st, base, d_offsets, n, valid, meta);
+        else
+            hipLaunchKernelGGL(gro_head_kernel<false>, dim3(hgrid), dim3(kBlock), 0, st, base, d_offsets, n, valid, meta);
+        hipLaunchKernelGGL(gro_scan_block_kernel<false>, dim3(nb), dim3(kBlock), 0, st, meta, n, per, sums, wdst, wlast,
+                           o);
+    }
+    hipLaunchKernelGGL(gro_scan_sums_kernel, dim3(1), dim3(kBlock), 0, st, sums, nb, o);
+    if (n) {
+        hipLaunchKernelGGL(gro_scan_block_kernel<true>, dim3(nb), dim3(kBlock), 0, st, meta, n, per, sums, wdst, wlast,
+                           o);
+        const int bpc = c.blocks_per_cu >= 1 && c.blocks_per_cu <= 8 ? c.blocks_per_cu : 8;
+        const uint64_t groups = ((uint64_t)n + kEmitGroup - 1) / kEmitGroup;
+        const uint32_t egrid = (uint32_t)std::min<uint64_t>((groups + kWavesPerBlock - 1) / kWavesPerBlock,
+                                                            (uint64_t)std::max(c.cus, 1) * bpc);
+        if (ipver == 6)
+            hipLaunchKernelGGL(gro_emit_kernel<true>, dim3(egrid), dim3(kBlock), 0, st, base, d_offsets, n, meta, wdst,
+                               wlast, o);
+        else
+            hipLaunchKernelGGL(gro_emit_kernel<false>, dim3(egrid), dim3(kBlock), 0, st, base, d_offsets, n, meta, wdst,
+                               wlast, o);
+    }
+    return hipGetLastError();
+}
+
+}  // namespace nsx

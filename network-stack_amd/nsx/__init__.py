@@ -127,13 +127,18 @@ def lib() -> ctypes.CDLL:
             "nsx_tso_ipv6_tcp_build_host": [vp, vp, vp, vp, vp, vp, vp, u64, vp, vp, u64, vp, vp, vp, i32],
             "nsx_tso_ipv4_tcp_build_host_tuned": [vp, vp, vp, vp, vp, vp, vp, u64, vp, vp, u64, vp, vp, vp, i32, vp],
             "nsx_tso_ipv6_tcp_build_host_tuned": [vp, vp, vp, vp, vp, vp, vp, u64, vp, vp, u64, vp, vp, vp, i32, vp],
+            "nsx_gro_work_bytes": [u64, ctypes.POINTER(u64)],
+            "nsx_gro_ipv4_tcp_dev": [vp, vp, u64, vp, vp, vp, u64, vp],
+            "nsx_gro_ipv6_tcp_dev": [vp, vp, u64, vp, vp, vp, u64, vp],
+            "nsx_gro_ipv4_tcp_dev_tuned": [vp, vp, u64, vp, vp, vp, u64, vp, vp],
+            "nsx_gro_ipv6_tcp_dev_tuned": [vp, vp, u64, vp, vp, vp, u64, vp, vp],
             "nsx_fixed_launch_count": [u64, u32, u64, vp, ctypes.POINTER(u64)],
             "nsx_ipv4_hdr_launch_count": [vp, u64, u32, u64, vp, ctypes.POINTER(u64)],
         }
         # present since ABI round 6, and the transmit pass since its own change; an older library (same-box A/B against a
         # previous build) lacks them
         optional = {"nsx_stream_release", "nsx_deal_sets_in_use"} | \
-            {k for k in sig if k.startswith(("nsx_tx_", "nsx_tso_"))}
+            {k for k in sig if k.startswith(("nsx_tx_", "nsx_tso_", "nsx_gro_"))}
         for name, args in sig.items():
             if name in optional and not hasattr(L, name):
                 continue
@@ -950,6 +955,79 @@ def tso_ipv6_tcp_build_host(ip: dict, fields: dict, data: np.ndarray, data_off: 
                             num_gpus: int = 0, tune=None):
     return _tso_build_host(6, ip, fields, data, data_off, mss, frame_first, frame_seg, out_off, opts, opt_off, out,
                            want_raw, num_gpus, tune)
+
+
+# ---------------------------------------------------------------------------
+# receive coalescing: frames in, super-segments in segmentation offload's format out (nsx_gro_*)
+# ---------------------------------------------------------------------------
+# nsx_gro_out members in order: (name, torch dtype, worst-case element count as a function of (n, alen, buf bytes))
+GRO_FIELDS = (("n_super", "int64", lambda n, a, b: 1),
+              ("src", "uint8", lambda n, a, b: n * a), ("dst", "uint8", lambda n, a, b: n * a),
+              ("ident", "int16", lambda n, a, b: n), ("ttl", "uint8", lambda n, a, b: n),
+              ("tclass", "uint8", lambda n, a, b: n), ("flow", "int32", lambda n, a, b: n),
+              ("src_port", "int16", lambda n, a, b: n), ("dst_port", "int16", lambda n, a, b: n),
+              ("seq_num", "int32", lambda n, a, b: n), ("ack_num", "int32", lambda n, a, b: n),
+              ("offset", "uint8", lambda n, a, b: n), ("control", "uint8", lambda n, a, b: n),
+              ("window", "int16", lambda n, a, b: n), ("urgent_ptr", "int16", lambda n, a, b: n),
+              ("mss", "int32", lambda n, a, b: n), ("opts", "uint8", lambda n, a, b: 40 * n),
+              ("opt_off", "int64", lambda n, a, b: n + 1), ("data", "uint8", lambda n, a, b: b),
+              ("data_off", "int64", lambda n, a, b: n + 1), ("first_frame", "int64", lambda n, a, b: n),
+              ("frame_cnt", "int32", lambda n, a, b: n), ("frame_seg", "int32", lambda n, a, b: n))
+
+
+class GroOut(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name, _, _ in GRO_FIELDS]
+
+
+def gro_work_bytes(n: int) -> int:
+    """nsx_gro_work_bytes: the scratch bytes one gro_ipv4_tcp_dev / gro_ipv6_tcp_dev call over n frames needs."""
+    c = ctypes.c_uint64(0)
+    _check(lib().nsx_gro_work_bytes(n, ctypes.byref(c)), "nsx_gro_work_bytes")
+    return c.value
+
+
+def _gro_dev(ipver: int, buf, offsets, valid, out, work, stream, tune) -> dict:
+    import torch
+    what = f"gro_ipv{ipver}_tcp_dev"
+    n = _count(offsets, f"{what} offsets")
+    alen = _ip_sizes(ipver)["src"]
+    _span(buf, 0, f"{what} buf", elem=1)
+    _span(valid, 8 * ((n + 63) // 64), f"{what} valid", elem=8)
+    if valid is None:
+        raise ValueError(f"{what}: the receive pass's mask `valid` is required")
+    res = dict(out or {})
+    bad = set(res) - {k for k, _, _ in GRO_FIELDS}
+    if bad:
+        raise ValueError(f"{what}: unknown output(s) {sorted(bad)}")
+    for k, dt, count in GRO_FIELDS:
+        need = count(n, alen, buf.numel())
+        if res.get(k) is None:  # worst-case size; never a zero-size tensor, whose address is NULL
+            res[k] = torch.empty(max(need, 1), dtype=getattr(torch, dt), device=offsets.device)
+        size = np.dtype(dt).itemsize
+        _span(res[k], need * size, f"{what} {k}", elem=size)
+    need = gro_work_bytes(n)
+    if work is None:
+        work = torch.empty(need, dtype=torch.uint8, device=offsets.device)
+    _span(work, need, f"{what} work")
+    soa = GroOut(*[_dev_ptr(res[k]) for k, _, _ in GRO_FIELDS])
+    fn = getattr(lib(), f"nsx_gro_ipv{ipver}_tcp_dev_tuned")
+    _check(fn(_dev_ptr(buf), _dev_ptr(offsets), n, _dev_ptr(valid), ctypes.byref(soa), _dev_ptr(work),
+              work.numel() * work.element_size(), _stream(stream), _tune(tune)), f"nsx_{what}")
+    return res
+
+
+def gro_ipv4_tcp_dev(buf, offsets, valid, out=None, work=None, stream=None, tune=None) -> dict:
+    """TCP receive coalescing over packed IPv4/TCP frames: buf / offsets as rx_ipv4_tcp_verify_dev, valid = that
+    pass's mask. Returns a dict of device tensors, the members of nsx_gro_out (GRO_FIELDS) — n_super (one int64),
+    the per-super-segment arrays tso_ipv4_tcp_build_dev takes, first_frame / frame_cnt, and frame_seg per frame —
+    allocated at worst-case size (n entries, n + 1 offsets, buf.numel() data bytes, 40·n option bytes) unless given
+    in `out`; `work` is scratch of gro_work_bytes(n) bytes. Does not synchronise: n_super is in device memory."""
+    return _gro_dev(4, buf, offsets, valid, out, work, stream, tune)
+
+
+def gro_ipv6_tcp_dev(buf, offsets, valid, out=None, work=None, stream=None, tune=None) -> dict:
+    """The same for IPv6 (src / dst 16 bytes per super-segment; ident 0; tclass and flow from the header)."""
+    return _gro_dev(6, buf, offsets, valid, out, work, stream, tune)
 
 
 def fill_splitmix64_dev(buf, seed: int, byte_off: int = 0, stream=None):
