@@ -418,9 +418,11 @@ int nsx_rx_ipv6_tcp_verify_dev(const void* d_base, const uint64_t* d_offsets, ui
  * [200]). A member that does not join is a head. Super-segments are numbered in
  * frame order; n_super = the number of heads.
  *
- * Coalescing is by adjacency only: callers deliver a flow's frames in arrival
- * order per queue; there is no flow table for interleaved flows. A super-segment
- * has no IP length field, so there is no 64 KiB cap on it.
+ * Coalescing is by adjacency only: these calls keep no flow table, so they merge
+ * a flow's frames only where they arrive back to back. For a queue on which many
+ * connections interleave, nsx_gro_flow_ipv4_tcp_dev / nsx_gro_flow_ipv6_tcp_dev
+ * below coalesce per connection. A super-segment has no IP length field, so
+ * there is no 64 KiB cap on it.
  *
  * Every member of nsx_gro_out is a writable device array and required. For
  * super-segment s with first frame f and last frame l, all written:
@@ -489,6 +491,60 @@ int nsx_gro_ipv4_tcp_dev(const void* d_base, const uint64_t* d_offsets, uint64_t
                          const nsx_gro_out* out, void* d_work, uint64_t work_bytes, nsx_stream_t stream);
 int nsx_gro_ipv6_tcp_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n, const uint64_t* d_valid,
                          const nsx_gro_out* out, void* d_work, uint64_t work_bytes, nsx_stream_t stream);
+
+/* Flow-keyed receive coalescing: nsx_gro_* per connection, however the
+ * connections interleave in the batch (RSS hashes many connections onto one
+ * queue). The frames are put in a stable order by a 32-bit flow key, and the
+ * rules above, unchanged, run over that order. A key collision therefore never
+ * makes a wrong merge — same() still compares every field — it only costs
+ * merges. Arguments as nsx_gro_*, plus d_order (n entries, an output).
+ *
+ * Flow key. The key of a non-member (Member above) is 0xFFFFFFFF; a frame whose
+ * d_valid bit is clear is not read at all, and of a frame whose bit is set at
+ * most the IP header and the first 16 TCP bytes are read, never a byte outside
+ * the frame's own range. For a member take these little-endian dwords in order:
+ * IPv4 the IP header's bytes 12-15 and 16-19 (src, dst), IPv6 its bytes 8-39
+ * (8 dwords); then TCP bytes 0-3 (the ports). h = 0x811C9DC5; for each dword w,
+ * h = ((h ^ w) * 0x01000193) mod 2^32; key = h. A member whose hash happens to
+ * be 0xFFFFFFFF keeps that key: it sorts among the non-members and merely loses
+ * merges.
+ *
+ * Order. d_order = the stable ascending sort of the frame indices 0..n-1 by
+ * key: equal keys keep arrival order (numpy.argsort(keys, kind="stable"), bit
+ * for bit). So a connection's frames become consecutive, in arrival order;
+ * super-segments come out grouped by key, not by arrival; non-members come last.
+ *
+ * Outputs. Let B' be the batch whose frame p is frame d_order[p] of the input,
+ * with valid'[p] = valid[d_order[p]]. Every member of nsx_gro_out is exactly
+ * what nsx_gro_ipvX_tcp_dev writes over B' — the regions left untouched
+ * included — except:
+ *   first_frame[s] is a position: super-segment s consists of the frames
+ *     d_order[first_frame[s] + j], 0 <= j < frame_cnt[s];
+ *   frame_seg stays indexed by the original frame:
+ *     frame_seg[d_order[p]] = frame_seg'[p].
+ * Fed to nsx_tso_*_build_dev (frame_first = the prefix sum of frame_cnt,
+ * frame_seg = frame_seg', that is frame_seg gathered through d_order), the
+ * outputs rebuild at output position p frame d_order[p] byte for byte, for the
+ * frames the transmit pass can express (the condition above).
+ *
+ * nsx_gro_flow_work_bytes(n) >= nsx_gro_work_bytes(n) gives the scratch, for
+ * every tune setting. NSX_EINVAL before any launch: a NULL pointer or member
+ * (d_base, d_valid and d_order may be NULL when n == 0), n >= 2^32 - 1,
+ * work_bytes too small. Then NSX_ENODEV without a GPU. n == 0 behaves as
+ * nsx_gro_* and does not write d_order. No allocation, no host sync, no
+ * per-stream counters; the call is one serial chain of launches and can be
+ * captured into a graph. The return type stands on a line of its own in these
+ * declarations: nsx_gro_* above is a closed set of three. */
+int
+nsx_gro_flow_work_bytes(uint64_t n, uint64_t* out);
+int
+nsx_gro_flow_ipv4_tcp_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n, const uint64_t* d_valid,
+                          uint32_t* d_order, const nsx_gro_out* out, void* d_work, uint64_t work_bytes,
+                          nsx_stream_t stream);
+int
+nsx_gro_flow_ipv6_tcp_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n, const uint64_t* d_valid,
+                          uint32_t* d_order, const nsx_gro_out* out, void* d_work, uint64_t work_bytes,
+                          nsx_stream_t stream);
 
 /* ----------------------------------------------------------------------------
  * Host-resident batches: pinned staging, H2D → kernel → D2H double-buffered

@@ -470,30 +470,43 @@ NSX_TSO_DEV(4)
 NSX_TSO_DEV(6)
 #undef NSX_TSO_DEV
 
-// ---- receive coalescing: everything validated on the host, then the five launches of gro_kernels.hip ----
+// ---- receive coalescing: everything validated on the host, then the five launches of gro_kernels.hip (the
+// flow-keyed calls: the key pass and the sort of gro_flow_kernels.hip before them) ----
 int nsx_gro_work_bytes(uint64_t n, uint64_t* out) {
     if (!out || n >= 0xFFFFFFFFull) return NSX_EINVAL;
     *out = nsx::gro_work_bytes(n);
     return NSX_OK;
 }
 
-static int gro_dev(int ipver, const void* d_base, const uint64_t* d_offsets, uint64_t n, const uint64_t* d_valid,
-                   const nsx_gro_out* o, void* d_work, uint64_t work_bytes, nsx_stream_t stream,
-                   const nsx_tune* tune) {
-    // an empty batch has no frame bytes and no mask words
+int nsx_gro_flow_work_bytes(uint64_t n, uint64_t* out) {
+    if (!out || n >= 0xFFFFFFFFull) return NSX_EINVAL;
+    *out = nsx::gro_flow_work_bytes(n);
+    return NSX_OK;
+}
+
+// flow: the flow-keyed call (nsx_gro_flow_*: the key pass and the sort of gro_flow_kernels.hip first, d_order an
+// output), else coalescing by adjacency
+static int gro_dev(int ipver, bool flow, const void* d_base, const uint64_t* d_offsets, uint64_t n,
+                   const uint64_t* d_valid, uint32_t* d_order, const nsx_gro_out* o, void* d_work, uint64_t work_bytes,
+                   nsx_stream_t stream, const nsx_tune* tune) {
+    // an empty batch has no frame bytes, no mask words and no order
     if ((n && (!d_base || !d_valid)) || !d_offsets || !d_work || !o || n >= 0xFFFFFFFFull) return NSX_EINVAL;
+    if (flow && n && !d_order) return NSX_EINVAL;
     if (!o->n_super || !o->src || !o->dst || !o->ident || !o->ttl || !o->tclass || !o->flow || !o->src_port ||
         !o->dst_port || !o->seq_num || !o->ack_num || !o->offset || !o->control || !o->window || !o->urgent_ptr ||
         !o->mss || !o->opts || !o->opt_off || !o->data || !o->data_off || !o->first_frame || !o->frame_cnt ||
         !o->frame_seg)
         return NSX_EINVAL;
-    if (work_bytes < nsx::gro_work_bytes(n)) return NSX_EINVAL;
+    if (work_bytes < (flow ? nsx::gro_flow_work_bytes(n) : nsx::gro_work_bytes(n))) return NSX_EINVAL;
     const int dev = current_device();
     if (dev < 0) return NSX_ENODEV;
     const nsx::GroOut g{o->n_super, o->src,      o->dst,         o->ident,     o->ttl,     o->tclass,
                         o->flow,    o->src_port, o->dst_port,    o->seq_num,   o->ack_num, o->offset,
                         o->control, o->window,   o->urgent_ptr,  o->mss,       o->opts,    o->opt_off,
                         o->data,    o->data_off, o->first_frame, o->frame_cnt, o->frame_seg};
+    if (flow)
+        return map_err(nsx::launch_gro_flow(make_cfg(dev, tune), ipver, d_base, d_offsets, n, d_valid, d_order, g,
+                                            d_work, static_cast<hipStream_t>(stream)));
     return map_err(nsx::launch_gro(make_cfg(dev, tune), ipver, d_base, d_offsets, n, d_valid, g, d_work,
                                    static_cast<hipStream_t>(stream)));
 }
@@ -501,12 +514,23 @@ static int gro_dev(int ipver, const void* d_base, const uint64_t* d_offsets, uin
 #define NSX_GRO_DEV(V)                                                                                             \
     int nsx_gro_ipv##V##_tcp_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n, const uint64_t* d_valid, \
                                  const nsx_gro_out* out, void* d_work, uint64_t work_bytes, nsx_stream_t stream) {  \
-        return gro_dev(V, d_base, d_offsets, n, d_valid, out, d_work, work_bytes, stream, nullptr);                \
+        return gro_dev(V, false, d_base, d_offsets, n, d_valid, nullptr, out, d_work, work_bytes, stream, nullptr); \
     }                                                                                                              \
     int nsx_gro_ipv##V##_tcp_dev_tuned(const void* d_base, const uint64_t* d_offsets, uint64_t n,                   \
                                        const uint64_t* d_valid, const nsx_gro_out* out, void* d_work,              \
                                        uint64_t work_bytes, nsx_stream_t stream, const nsx_tune* tune) {           \
-        return gro_dev(V, d_base, d_offsets, n, d_valid, out, d_work, work_bytes, stream, tune);                   \
+        return gro_dev(V, false, d_base, d_offsets, n, d_valid, nullptr, out, d_work, work_bytes, stream, tune);   \
+    }                                                                                                              \
+    int nsx_gro_flow_ipv##V##_tcp_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n,                    \
+                                      const uint64_t* d_valid, uint32_t* d_order, const nsx_gro_out* out,          \
+                                      void* d_work, uint64_t work_bytes, nsx_stream_t stream) {                    \
+        return gro_dev(V, true, d_base, d_offsets, n, d_valid, d_order, out, d_work, work_bytes, stream, nullptr); \
+    }                                                                                                              \
+    int nsx_gro_flow_ipv##V##_tcp_dev_tuned(const void* d_base, const uint64_t* d_offsets, uint64_t n,              \
+                                            const uint64_t* d_valid, uint32_t* d_order, const nsx_gro_out* out,    \
+                                            void* d_work, uint64_t work_bytes, nsx_stream_t stream,                \
+                                            const nsx_tune* tune) {                                                \
+        return gro_dev(V, true, d_base, d_offsets, n, d_valid, d_order, out, d_work, work_bytes, stream, tune);    \
     }
 NSX_GRO_DEV(4)
 NSX_GRO_DEV(6)

@@ -1,5 +1,6 @@
 // csum_kernels.h — internal launcher interface between the C ABI (csum_api.cpp,
-// host_batch.cpp) and the gfx950 kernels (csum_kernels.hip, gro_kernels.hip). Not a public header.
+// host_batch.cpp) and the gfx950 kernels (csum_kernels.hip, gro_kernels.hip, gro_flow_kernels.hip). Not a public
+// header.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -17,7 +18,7 @@ struct LaunchCfg {
     int blocks_per_cu = 0;    // persistent grid = cus × blocks_per_cu blocks of 256 threads
     int segs_per_wave = 0;    // fixed short-segment paths: segments per wave task (1, 2, 4, 8)
     int block_mode = 0;       // 0 auto (a block per segment when n < 4·cus), 1 never, 2 always
-    int rows = 0;             // ragged scan kernel: 1 KiB rows per batch (4, 8, 16)
+    int rows = 0;             // ragged scan kernel: 1 KiB rows per batch (4, 8, 16); flow GRO: 256-key rows per sort tile
     int run_segs = 0;         // ragged scan kernel: segments per wave task (1..63)
     int xcd_chunk = 0;        // XCD deal: 0 auto, 1..20 = chunks of 2^k tasks, else contiguous eighths
     int64_t window_bytes = 0; // fixed short-segment path: back-to-back launches of ≤ this many bytes (0 auto, -1 one)
@@ -119,6 +120,19 @@ uint64_t gro_work_bytes(uint64_t n);
 // scan block (0 = 4096, clamped to 16..65536), c.blocks_per_cu = the copy kernel's grid (default 8).
 hipError_t launch_gro(const LaunchCfg& c, int ipver, const void* d_base, const uint64_t* d_offsets, uint64_t n,
                       const uint64_t* valid, const GroOut& o, void* work, hipStream_t st);
+// The same passes over the batch whose frame p is frame order[p] of the input (n entries, a permutation of 0..n-1):
+// offsets, the valid bit and frame_seg go through the order; first_frame holds positions (gro_kernels.hip).
+hipError_t launch_gro_ordered(const LaunchCfg& c, int ipver, const void* d_base, const uint64_t* d_offsets, uint64_t n,
+                              const uint64_t* valid, const uint32_t* order, const GroOut& o, void* work,
+                              hipStream_t st);
+// Flow-keyed receive coalescing (nsx_gro_flow_*, gro_flow_kernels.hip): scratch bytes of one launch_gro_flow over n
+// frames (whatever the tune; >= gro_work_bytes(n)).
+uint64_t gro_flow_work_bytes(uint64_t n);
+// Key pass, stable radix sort of the frame indices by key into d_order, then launch_gro_ordered: one serial chain
+// of launches. n == 0 writes no order. c.rows = keys per sort tile in units of 256 (0 = the default, clamped to
+// 1..64).
+hipError_t launch_gro_flow(const LaunchCfg& c, int ipver, const void* d_base, const uint64_t* d_offsets, uint64_t n,
+                           const uint64_t* valid, uint32_t* d_order, const GroOut& o, void* work, hipStream_t st);
 struct TcpParsedSoA {  // device arrays, one entry per segment; every member nullable
     uint16_t* src_port;
     uint16_t* dst_port;

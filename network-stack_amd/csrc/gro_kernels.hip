@@ -15,6 +15,12 @@
 //          destination) byte shift, 16-byte stores at destination-aligned addresses, byte / short / dword stores
 //          at the two ends (two frames' payloads may meet inside one dword, so nothing is read back). The lane
 //          that owns a head frame also writes the super-segment's fields and option bytes.
+//
+// head, apply and emit are templates on ORDERED. Not ORDERED is nsx_gro_*: position = frame, the kernels as they
+// always were (the order pointer is never read). ORDERED serves nsx_gro_flow_* (gro_flow_kernels.hip sorts the
+// frame indices by flow key first): position p of the batch is frame order[p] — offsets[f], offsets[f + 1] and
+// the valid bit of f go through the order, meta / wdst / wlast stay in position space, frame_seg is scattered to f
+// and first_frame holds positions.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -46,32 +52,14 @@ __device__ __forceinline__ bool gro_join(uint32_t m0, uint32_t m1, uint32_t m2) 
     return (m0 & kSame) && p0 >= 1u && p0 <= p1 && !((m1 & kSame) && p1 < p2);
 }
 
-__device__ __forceinline__ uint32_t bswap16(uint32_t v) { return ((v & 0xFFu) << 8) | ((v >> 8) & 0xFFu); }
-__device__ __forceinline__ uint32_t bswap32(uint32_t v) { return __builtin_bswap32(v); }
-
-// A frame's bytes as dwords: the window starts at the frame's address rounded down to 4 bytes; a dword that
-// holds no byte of the frame is not loaded and reads 0 (an aligned dword holding a readable byte never crosses a
-// page). at(b): the little-endian dword at frame byte b (a multiple of 4).
-struct FrameWin {
-    const uint32_t* w;
-    uint32_t sh, end;  // frame start inside the first dword; window bytes up to the frame's end
-    __device__ __forceinline__ uint32_t word(uint32_t k) const { return 4u * k < end ? w[k] : 0u; }
-    __device__ __forceinline__ uint32_t at(uint32_t b) const {
-        const uint32_t k = b >> 2;
-        return __builtin_amdgcn_alignbyte(word(k + 1), word(k), sh);
-    }
-};
-
-__device__ __forceinline__ FrameWin frame_win(const uint8_t* p, uint32_t flen) {
-    const uint32_t sh = (uint32_t)((uintptr_t)p & 3u);
-    return FrameWin{reinterpret_cast<const uint32_t*>(p - sh), sh, flen ? sh + flen : 0u};
-}
-
 // ------------------------------------------------------------------------------------------------ head pass
-template <bool V6>
+// ORDERED (nsx_gro_flow_*): position p of the batch is frame order[p] — its offsets and its valid bit go through
+// the order, meta stays in position space. Not ORDERED: order is unused and the kernel is the one it was.
+template <bool V6, bool ORDERED>
 __global__ __launch_bounds__(kBlock) void gro_head_kernel(const uint8_t* __restrict__ base,
                                                           const uint64_t* __restrict__ offsets, uint32_t n,
                                                           const uint64_t* __restrict__ valid,
+                                                          const uint32_t* __restrict__ order,
                                                           uint32_t* __restrict__ meta) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t wave = (uint64_t)blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6);
@@ -79,7 +67,9 @@ __global__ __launch_bounds__(kBlock) void gro_head_kernel(const uint8_t* __restr
     if (first >= n) return;                     // wave-uniform
     const int64_t fi = (int64_t)first + lane - 1;
     const bool live = fi >= 0 && fi < (int64_t)n;
-    const uint32_t i = live ? (uint32_t)fi : 0u;
+    const uint32_t p = live ? (uint32_t)fi : 0u;  // the position; i: the frame
+    uint32_t i = p;
+    if constexpr (ORDERED) i = live ? order[p] : 0u;
     const uint64_t o0 = live ? offsets[i] : 0u, o1 = live ? offsets[(uint64_t)i + 1] : 0u;
     // a frame longer than any length field can say is no member; the cap keeps the window arithmetic in 32 bits
     const uint32_t flen = live ? (uint32_t)min(o1 - o0, (uint64_t)0x20000u) : 0u;
@@ -89,6 +79,9 @@ __global__ __launch_bounds__(kBlock) void gro_head_kernel(const uint8_t* __restr
     constexpr int NK = V6 ? 10 : 4;  // IP words that must be equal
     uint32_t K[NK];
     uint32_t iph, seg, ident = 0;
+    // The membership test is written out here, not taken from kernel_util.h's frame_wellformed / tcp_doff_fits (the
+    // same conditions, which the key pass of gro_flow_kernels.hip uses): through the helpers hipcc schedules this
+    // kernel differently, and the instantiations behind nsx_gro_* are kept instruction for instruction what they were.
     bool ok;
     if constexpr (V6) {
         const uint32_t h0 = F.at(0), h1 = F.at(4);
@@ -149,7 +142,7 @@ __global__ __launch_bounds__(kBlock) void gro_head_kernel(const uint8_t* __restr
     same = same && (pctl & 0x2Fu) == 0u && (ctl & 0xA6u) == 0u && ((ctl ^ pctl) & 0x76u) == 0u;
 
     if (live && lane >= 1u)
-        meta[i] = member ? pay | (optdw << kOptShift) | ((iph + doff * 4u) << kHdrShift) | (same ? kSame : 0u) | kMember
+        meta[p] = member ? pay | (optdw << kOptShift) | ((iph + doff * 4u) << kHdrShift) | (same ? kSame : 0u) | kMember
                          : 0u;
 }
 
@@ -201,11 +194,13 @@ __device__ __forceinline__ GroFrame gro_frame(const uint32_t* __restrict__ meta,
 
 // APPLY false: sums[3b..] = the block's (heads, option bytes of heads, payload bytes). APPLY true: sums holds the
 // exclusive prefix of those over the blocks, and the per-frame and per-head outputs are written.
-template <bool APPLY>
+// ORDERED (with APPLY): i is a position; frame_seg is scattered to the frame order[i], all else stays by position.
+template <bool APPLY, bool ORDERED>
 __global__ __launch_bounds__(kBlock) void gro_scan_block_kernel(const uint32_t* __restrict__ meta, uint32_t n,
                                                                 uint32_t per_block, uint64_t* __restrict__ sums,
                                                                 uint64_t* __restrict__ wdst,
-                                                                uint32_t* __restrict__ wlast, GroOut o) {
+                                                                uint32_t* __restrict__ wlast,
+                                                                const uint32_t* __restrict__ order, GroOut o) {
     __shared__ uint64_t lds[kWavesPerBlock][3];
     const uint64_t lo = (uint64_t)blockIdx.x * per_block, hi = min(lo + per_block, (uint64_t)n);
     uint64_t carry[3] = {0, 0, 0};
@@ -224,7 +219,7 @@ __global__ __launch_bounds__(kBlock) void gro_scan_block_kernel(const uint32_t* 
         if (APPLY && live) {
             const bool member = f.m & kMember;
             const uint32_t s = (uint32_t)(carry[0] + v[0]) + f.head - 1u;
-            o.frame_seg[i] = member ? s : 0xFFFFFFFFu;
+            o.frame_seg[ORDERED ? order[i] : i] = member ? s : 0xFFFFFFFFu;
             wdst[i] = carry[2] + v[2];
             if (f.head) {
                 o.first_frame[s] = i;
@@ -367,10 +362,11 @@ __device__ __forceinline__ void store_pair(const CopyJob& j, uint32_t c0, uint32
 }
 
 // The fields and option bytes of the super-segment s whose first frame is i (one lane).
-template <bool V6>
+template <bool V6, bool ORDERED>
 __device__ __forceinline__ void emit_head(const uint8_t* __restrict__ base, const uint64_t* __restrict__ offsets,
                                           const uint32_t* __restrict__ meta, const uint32_t* __restrict__ wlast,
-                                          const GroOut& o, uint32_t i, uint32_t s, uint32_t m, uint64_t off) {
+                                          const uint32_t* __restrict__ order, const GroOut& o, uint32_t i, uint32_t s,
+                                          uint32_t m, uint64_t off) {
     const uint32_t optb = m_optb(m), hdr = m_hdr(m), pay = m_pay(m);
     const uint32_t iph = hdr - 20u - optb;
     const FrameWin F = frame_win(base + off, hdr + pay);
@@ -421,7 +417,7 @@ __device__ __forceinline__ void emit_head(const uint8_t* __restrict__ base, cons
     uint32_t ctl = (t3 >> 8) & 0xFFu;
     if (l != i) {  // FIN / PSH of the run's last frame: its control byte, 13 bytes into its TCP header
         const uint32_t ml = meta[l];
-        ctl |= base[offsets[l] + (m_hdr(ml) - 20u - m_optb(ml)) + 13u] & 0x09u;
+        ctl |= base[offsets[ORDERED ? order[l] : l] + (m_hdr(ml) - 20u - m_optb(ml)) + 13u] & 0x09u;
     }
     o.control[s] = (uint8_t)ctl;
     uint8_t* op = o.opts + o.opt_off[s];
@@ -436,12 +432,15 @@ __device__ __forceinline__ void emit_head(const uint8_t* __restrict__ base, cons
     }
 }
 
-template <bool V6>
+// ORDERED: lane j's frame is order[g0 + j]; its offset and its frame_seg entry go through the order, meta, wdst,
+// wlast and first_frame are by position.
+template <bool V6, bool ORDERED>
 __global__ __launch_bounds__(kBlock) void gro_emit_kernel(const uint8_t* __restrict__ base,
                                                           const uint64_t* __restrict__ offsets, uint32_t n,
                                                           const uint32_t* __restrict__ meta,
                                                           const uint64_t* __restrict__ wdst,
-                                                          const uint32_t* __restrict__ wlast, GroOut o) {
+                                                          const uint32_t* __restrict__ wlast,
+                                                          const uint32_t* __restrict__ order, GroOut o) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t nwaves = (uint64_t)gridDim.x * kWavesPerBlock;
     const uint64_t groups = ((uint64_t)n + kEmitGroup - 1u) / kEmitGroup;
@@ -451,10 +450,12 @@ __global__ __launch_bounds__(kBlock) void gro_emit_kernel(const uint8_t* __restr
         const bool own = lane < cnt;
         const uint32_t i = g0 + (own ? lane : 0u);
         const uint32_t m = own ? meta[i] : 0u;
-        const uint64_t off = own ? offsets[i] : 0u, dst = own ? wdst[i] : 0u;
+        uint32_t f = i;  // the frame at position i
+        if constexpr (ORDERED) f = own ? order[i] : 0u;
+        const uint64_t off = own ? offsets[f] : 0u, dst = own ? wdst[i] : 0u;
         if (m & kMember) {
-            const uint32_t s = o.frame_seg[i];
-            if (o.first_frame[s] == i) emit_head<V6>(base, offsets, meta, wlast, o, i, s, m, off);
+            const uint32_t s = o.frame_seg[f];
+            if (o.first_frame[s] == i) emit_head<V6, ORDERED>(base, offsets, meta, wlast, order, o, i, s, m, off);
         }
         // The group's payloads as one stream of row pairs (2 KiB of destination each), software-pipelined: the
         // loads of the next pair — of this frame, or the first of the next frame with a payload — are issued
@@ -503,8 +504,12 @@ GroWork gro_layout(uint64_t n) {
 
 uint64_t gro_work_bytes(uint64_t n) { return gro_layout(n).total; }
 
-hipError_t launch_gro(const LaunchCfg& c, int ipver, const void* d_base, const uint64_t* d_offsets, uint64_t n64,
-                      const uint64_t* valid, const GroOut& o, void* work, hipStream_t st) {
+namespace {
+
+template <bool ORDERED>
+hipError_t launch_gro_passes(const LaunchCfg& c, int ipver, const void* d_base, const uint64_t* d_offsets, uint64_t n64,
+                             const uint64_t* valid, const uint32_t* order, const GroOut& o, void* work,
+                             hipStream_t st) {
     const uint32_t n = (uint32_t)n64;  // n < 2^32 - 1 (csum_api.cpp)
     const GroWork L = gro_layout(n);
     uint8_t* w = reinterpret_cast<uint8_t*>(((uintptr_t)work + 7u) & ~(uintptr_t)7u);
@@ -519,28 +524,44 @@ hipError_t launch_gro(const LaunchCfg& c, int ipver, const void* d_base, const u
         const uint64_t hw = ((uint64_t)n + kHeadFrames - 1) / kHeadFrames;
         const uint32_t hgrid = (uint32_t)((hw + kWavesPerBlock - 1) / kWavesPerBlock);
         if (ipver == 6)
-            hipLaunchKernelGGL(gro_head_kernel<true>, dim3(hgrid), dim3(kBlock), 0, st, base, d_offsets, n, valid, meta);
+            hipLaunchKernelGGL((gro_head_kernel<true, ORDERED>), dim3(hgrid), dim3(kBlock), 0, st, base, d_offsets, n,
+                               valid, order, meta);
         else
-            hipLaunchKernelGGL(gro_head_kernel<false>, dim3(hgrid), dim3(kBlock), 0, st, base, d_offsets, n, valid, meta);
-        hipLaunchKernelGGL(gro_scan_block_kernel<false>, dim3(nb), dim3(kBlock), 0, st, meta, n, per, sums, wdst, wlast,
-                           o);
+            hipLaunchKernelGGL((gro_head_kernel<false, ORDERED>), dim3(hgrid), dim3(kBlock), 0, st, base, d_offsets, n,
+                               valid, order, meta);
+        // the reduce pass reads meta only: one instantiation serves both
+        hipLaunchKernelGGL((gro_scan_block_kernel<false, false>), dim3(nb), dim3(kBlock), 0, st, meta, n, per, sums,
+                           wdst, wlast, order, o);
     }
     hipLaunchKernelGGL(gro_scan_sums_kernel, dim3(1), dim3(kBlock), 0, st, sums, nb, o);
     if (n) {
-        hipLaunchKernelGGL(gro_scan_block_kernel<true>, dim3(nb), dim3(kBlock), 0, st, meta, n, per, sums, wdst, wlast,
-                           o);
+        hipLaunchKernelGGL((gro_scan_block_kernel<true, ORDERED>), dim3(nb), dim3(kBlock), 0, st, meta, n, per, sums,
+                           wdst, wlast, order, o);
         const int bpc = c.blocks_per_cu >= 1 && c.blocks_per_cu <= 8 ? c.blocks_per_cu : 8;
         const uint64_t groups = ((uint64_t)n + kEmitGroup - 1) / kEmitGroup;
         const uint32_t egrid = (uint32_t)std::min<uint64_t>((groups + kWavesPerBlock - 1) / kWavesPerBlock,
                                                             (uint64_t)std::max(c.cus, 1) * bpc);
         if (ipver == 6)
-            hipLaunchKernelGGL(gro_emit_kernel<true>, dim3(egrid), dim3(kBlock), 0, st, base, d_offsets, n, meta, wdst,
-                               wlast, o);
+            hipLaunchKernelGGL((gro_emit_kernel<true, ORDERED>), dim3(egrid), dim3(kBlock), 0, st, base, d_offsets, n,
+                               meta, wdst, wlast, order, o);
         else
-            hipLaunchKernelGGL(gro_emit_kernel<false>, dim3(egrid), dim3(kBlock), 0, st, base, d_offsets, n, meta, wdst,
-                               wlast, o);
+            hipLaunchKernelGGL((gro_emit_kernel<false, ORDERED>), dim3(egrid), dim3(kBlock), 0, st, base, d_offsets, n,
+                               meta, wdst, wlast, order, o);
     }
     return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_gro(const LaunchCfg& c, int ipver, const void* d_base, const uint64_t* d_offsets, uint64_t n,
+                      const uint64_t* valid, const GroOut& o, void* work, hipStream_t st) {
+    return launch_gro_passes<false>(c, ipver, d_base, d_offsets, n, valid, nullptr, o, work, st);
+}
+
+hipError_t launch_gro_ordered(const LaunchCfg& c, int ipver, const void* d_base, const uint64_t* d_offsets, uint64_t n,
+                              const uint64_t* valid, const uint32_t* order, const GroOut& o, void* work,
+                              hipStream_t st) {
+    return launch_gro_passes<true>(c, ipver, d_base, d_offsets, n, valid, order, o, work, st);
 }
 
 }  // namespace nsx

@@ -1,6 +1,7 @@
-// kernel_util.h — device helpers shared by the kernel files (csum_kernels.hip, gro_kernels.hip): the wave / row
-// constants, the 16-byte chunk type, buffer descriptors and their 16-byte loads, byte masks and the v_alignbyte
-// realignment. Everything is __forceinline__ in an unnamed namespace, so each kernel file gets its own copies and
+// kernel_util.h — device helpers shared by the kernel files (csum_kernels.hip, gro_kernels.hip,
+// gro_flow_kernels.hip): the wave / row constants, the 16-byte chunk type, buffer descriptors and their 16-byte
+// loads, byte masks, the v_alignbyte realignment, and receive coalescing's clamped frame window (FrameWin) and
+// membership test. Everything is __forceinline__ in an unnamed namespace, so each kernel file gets its own copies and
 // the code generated for a kernel does not depend on which file defines the helper
 // (profiles/gro_kernels_vs_parent.txt). Not a public header; device code only.
 #pragma once
@@ -67,6 +68,55 @@ __device__ __forceinline__ uint32_t bperm(uint32_t v, uint32_t src_lane) {
 __device__ __forceinline__ u32x4 realign(u32x4 lo, uint32_t hi, uint32_t sh) {
     return u32x4{__builtin_amdgcn_alignbyte(lo.y, lo.x, sh), __builtin_amdgcn_alignbyte(lo.z, lo.y, sh),
                  __builtin_amdgcn_alignbyte(lo.w, lo.z, sh), __builtin_amdgcn_alignbyte(hi, lo.w, sh)};
+}
+
+__device__ __forceinline__ uint32_t bswap16(uint32_t v) { return ((v & 0xFFu) << 8) | ((v >> 8) & 0xFFu); }
+__device__ __forceinline__ uint32_t bswap32(uint32_t v) { return __builtin_bswap32(v); }
+
+// A frame's bytes as dwords: the window starts at the frame's address rounded down to 4 bytes; a dword that
+// holds no byte of the frame is not loaded and reads 0 (an aligned dword holding a readable byte never crosses a
+// page). at(b): the little-endian dword at frame byte b (a multiple of 4).
+struct FrameWin {
+    const uint32_t* w;
+    uint32_t sh, end;  // frame start inside the first dword; window bytes up to the frame's end
+    __device__ __forceinline__ uint32_t word(uint32_t k) const { return 4u * k < end ? w[k] : 0u; }
+    __device__ __forceinline__ uint32_t at(uint32_t b) const {
+        const uint32_t k = b >> 2;
+        return __builtin_amdgcn_alignbyte(word(k + 1), word(k), sh);
+    }
+};
+
+__device__ __forceinline__ FrameWin frame_win(const uint8_t* p, uint32_t flen) {
+    const uint32_t sh = (uint32_t)((uintptr_t)p & 3u);
+    return FrameWin{reinterpret_cast<const uint32_t*>(p - sh), sh, flen ? sh + flen : 0u};
+}
+
+// Well-formed as the receive pass of the IP version defines (include/nsx_csum.h: length, version, protocol and
+// fragment conditions), from the frame's length and its header dwords 0, 1 and 2 (h2: IPv4 only); iph = the IP
+// header's bytes, seg = the TCP segment's. One half of receive coalescing's membership test as the key pass of
+// gro_flow_kernels.hip makes it; the other is tcp_doff_fits below, on dword 3 of the TCP header. (The head pass of
+// gro_kernels.hip has the same conditions written out: see there.)
+template <bool V6>
+__device__ __forceinline__ bool frame_wellformed(uint32_t h0, uint32_t h1, uint32_t h2, uint32_t flen, uint32_t& iph,
+                                                 uint32_t& seg) {
+    bool ok;
+    if constexpr (V6) {
+        iph = 40u;
+        ok = flen >= 60u && (h0 & 0xF0u) == 0x60u && 40u + bswap16(h1) == flen && ((h1 >> 16) & 0xFFu) == 6u;
+        seg = flen - 40u;
+    } else {
+        iph = (h0 & 15u) * 4u;
+        ok = flen >= 40u && (h0 & 0xF0u) == 0x40u && iph >= 20u && iph <= flen && bswap16(h0 >> 16) == flen &&
+             (h1 & 0xFF3F0000u) == 0u && ((h2 >> 8) & 0xFFu) == 6u && flen - iph >= 20u;
+        seg = flen - iph;
+    }
+    return ok;
+}
+
+// 5 <= doff and doff*4 <= segment length, doff from TCP header dword 3 (bytes 12-15)
+__device__ __forceinline__ bool tcp_doff_fits(uint32_t t3, uint32_t seg) {
+    const uint32_t doff = (t3 >> 4) & 15u;
+    return doff >= 5u && doff * 4u <= seg;
 }
 
 }  // namespace

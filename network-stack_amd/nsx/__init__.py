@@ -132,6 +132,11 @@ def lib() -> ctypes.CDLL:
             "nsx_gro_ipv6_tcp_dev": [vp, vp, u64, vp, vp, vp, u64, vp],
             "nsx_gro_ipv4_tcp_dev_tuned": [vp, vp, u64, vp, vp, vp, u64, vp, vp],
             "nsx_gro_ipv6_tcp_dev_tuned": [vp, vp, u64, vp, vp, vp, u64, vp, vp],
+            "nsx_gro_flow_work_bytes": [u64, ctypes.POINTER(u64)],
+            "nsx_gro_flow_ipv4_tcp_dev": [vp, vp, u64, vp, vp, vp, vp, u64, vp],
+            "nsx_gro_flow_ipv6_tcp_dev": [vp, vp, u64, vp, vp, vp, vp, u64, vp],
+            "nsx_gro_flow_ipv4_tcp_dev_tuned": [vp, vp, u64, vp, vp, vp, vp, u64, vp, vp],
+            "nsx_gro_flow_ipv6_tcp_dev_tuned": [vp, vp, u64, vp, vp, vp, vp, u64, vp, vp],
             "nsx_fixed_launch_count": [u64, u32, u64, vp, ctypes.POINTER(u64)],
             "nsx_ipv4_hdr_launch_count": [vp, u64, u32, u64, vp, ctypes.POINTER(u64)],
         }
@@ -986,9 +991,17 @@ def gro_work_bytes(n: int) -> int:
     return c.value
 
 
-def _gro_dev(ipver: int, buf, offsets, valid, out, work, stream, tune) -> dict:
+def gro_flow_work_bytes(n: int) -> int:
+    """nsx_gro_flow_work_bytes: the scratch bytes one gro_flow_ipv4_tcp_dev / gro_flow_ipv6_tcp_dev call over n frames
+    needs (at least gro_work_bytes(n))."""
+    c = ctypes.c_uint64(0)
+    _check(lib().nsx_gro_flow_work_bytes(n, ctypes.byref(c)), "nsx_gro_flow_work_bytes")
+    return c.value
+
+
+def _gro_dev(ipver: int, buf, offsets, valid, out, work, stream, tune, flow: bool = False, order=None) -> dict:
     import torch
-    what = f"gro_ipv{ipver}_tcp_dev"
+    what = f"gro_flow_ipv{ipver}_tcp_dev" if flow else f"gro_ipv{ipver}_tcp_dev"
     n = _count(offsets, f"{what} offsets")
     alen = _ip_sizes(ipver)["src"]
     _span(buf, 0, f"{what} buf", elem=1)
@@ -1005,14 +1018,21 @@ def _gro_dev(ipver: int, buf, offsets, valid, out, work, stream, tune) -> dict:
             res[k] = torch.empty(max(need, 1), dtype=getattr(torch, dt), device=offsets.device)
         size = np.dtype(dt).itemsize
         _span(res[k], need * size, f"{what} {k}", elem=size)
-    need = gro_work_bytes(n)
+    if flow:
+        if order is None:  # never a zero-size tensor, whose address is NULL
+            order = torch.empty(max(n, 1), dtype=torch.int32, device=offsets.device)
+        _span(order, 4 * n, f"{what} order", elem=4)
+    need = gro_flow_work_bytes(n) if flow else gro_work_bytes(n)
     if work is None:
         work = torch.empty(need, dtype=torch.uint8, device=offsets.device)
     _span(work, need, f"{what} work")
     soa = GroOut(*[_dev_ptr(res[k]) for k, _, _ in GRO_FIELDS])
-    fn = getattr(lib(), f"nsx_gro_ipv{ipver}_tcp_dev_tuned")
-    _check(fn(_dev_ptr(buf), _dev_ptr(offsets), n, _dev_ptr(valid), ctypes.byref(soa), _dev_ptr(work),
-              work.numel() * work.element_size(), _stream(stream), _tune(tune)), f"nsx_{what}")
+    fn = getattr(lib(), f"nsx_{what}_tuned")
+    args = [_dev_ptr(buf), _dev_ptr(offsets), n, _dev_ptr(valid)] + ([_dev_ptr(order)] if flow else []) + \
+        [ctypes.byref(soa), _dev_ptr(work), work.numel() * work.element_size(), _stream(stream), _tune(tune)]
+    _check(fn(*args), f"nsx_{what}")
+    if flow:
+        res["order"] = order
     return res
 
 
@@ -1028,6 +1048,20 @@ def gro_ipv4_tcp_dev(buf, offsets, valid, out=None, work=None, stream=None, tune
 def gro_ipv6_tcp_dev(buf, offsets, valid, out=None, work=None, stream=None, tune=None) -> dict:
     """The same for IPv6 (src / dst 16 bytes per super-segment; ident 0; tclass and flow from the header)."""
     return _gro_dev(6, buf, offsets, valid, out, work, stream, tune)
+
+
+def gro_flow_ipv4_tcp_dev(buf, offsets, valid, out=None, order=None, work=None, stream=None, tune=None) -> dict:
+    """Flow-keyed receive coalescing over packed IPv4/TCP frames (nsx_gro_flow_ipv4_tcp_dev): gro_ipv4_tcp_dev per
+    connection, however the connections interleave in the batch. Returns the GRO_FIELDS dict plus "order" (n int32:
+    the stable sort of the frame indices by flow key, allocated unless given). first_frame holds positions in
+    `order`, frame_seg stays indexed by the original frame. `work` is scratch of gro_flow_work_bytes(n) bytes;
+    tune: run_segs and blocks_per_cu as gro_ipv4_tcp_dev, rows = keys per sort tile in units of 256."""
+    return _gro_dev(4, buf, offsets, valid, out, work, stream, tune, flow=True, order=order)
+
+
+def gro_flow_ipv6_tcp_dev(buf, offsets, valid, out=None, order=None, work=None, stream=None, tune=None) -> dict:
+    """The same for IPv6."""
+    return _gro_dev(6, buf, offsets, valid, out, work, stream, tune, flow=True, order=order)
 
 
 def fill_splitmix64_dev(buf, seed: int, byte_off: int = 0, stream=None):
