@@ -76,10 +76,14 @@ typedef struct nsx_tune {
                                   eighth dealt to the waves from the stream's counters where the stream allows
                                   it (nsx_csum.h, nsx_rx_ipv4_tcp_verify_dev), -1 = equal static shares
                                   throughout (A/B; replaces round 5's NSX_NO_DEAL build) */
-    int32_t chunk_bytes;       /* the sender-side host calls (nsx_tcp_build_host, nsx_tx_*_build_host,
-                                  nsx_tso_*_build_host): bytes of images, and of payload, per double-buffered
-                                  chunk; 0 = 64 MiB. A segment (or super-segment) larger than this is a chunk
-                                  of its own. Tests reach the multi-chunk path with small batches */
+    int32_t chunk_bytes;       /* every host call: bytes per double-buffered chunk; 0 = 64 MiB. Fixed stride:
+                                  max(1, chunk_bytes / max(stride, seg_len, 1)) segments per chunk. Ragged: a
+                                  segment larger than this is a chunk of its own. Receive (nsx_rx_*_host):
+                                  whole 64-frame mask words, never fewer than 64 frames but in a shard's last
+                                  chunk. Sender (nsx_tcp_build_host, nsx_tx_*_build_host, nsx_tso_*_build_host):
+                                  bytes of images, and of payload; a segment (or super-segment) larger than
+                                  this is a chunk of its own. Tests reach the multi-chunk path with small
+                                  batches */
     int32_t reserved[4];
 } nsx_tune;
 

@@ -7,29 +7,44 @@
 // checksum on the CPU: with no GPU the batch calls return NSX_ENODEV.
 #include <hip/hip_runtime_api.h>
 
-#include <algorithm>
-#include <cstring>
 #include <mutex>
-#include <thread>
-#include <vector>
 
 #include "../../include/nsx_csum.h"
 #include "../../include/nsx_tune.h"
+#include "api_util.h"
 #include "csum_kernels.h"
 #include "host_csum.h"
+#include "host_plan.h"
 
 namespace {
 
 constexpr int kMaxDevices = 64;
 
-struct DevInfo {
-    int cus = 0;
-    bool ok = false;
-};
-DevInfo g_dev[kMaxDevices];
+int g_cus[kMaxDevices];  // compute units per device, 0 = unusable; queried once
 std::once_flag g_dev_once[kMaxDevices];
 
-int device_count_raw() {
+// Current device of the calling thread, or -1 when there is no usable GPU.
+int current_device() {
+    if (nsx::device_count() <= 0) return -1;
+    int d = -1;
+    if (hipGetDevice(&d) != hipSuccess) {
+        (void)hipGetLastError();
+        return -1;
+    }
+    return nsx::device_cus(d) > 0 ? d : -1;
+}
+
+using nsx::map_err;
+using nsx::to_soa;
+
+nsx::LaunchCfg make_cfg(int dev, const nsx_tune* t) { return nsx::launch_cfg(nsx::device_cus(dev), t); }
+uint32_t aux_blocks(int dev) { return (uint32_t)nsx::device_cus(dev) * 8; }  // grid bound of the small helper kernels
+
+}  // namespace
+
+namespace nsx {
+
+int device_count() {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) {
         (void)hipGetLastError();
@@ -38,36 +53,25 @@ int device_count_raw() {
     return n;
 }
 
-const DevInfo* dev_info(int dev) {
-    if (dev < 0 || dev >= kMaxDevices) return nullptr;
+int device_cus(int dev) {
+    if (dev < 0 || dev >= kMaxDevices) return 0;
     std::call_once(g_dev_once[dev], [dev] {
         int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) {
-            g_dev[dev].cus = cus;
-            g_dev[dev].ok = true;
-        } else {
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
+            g_cus[dev] = cus;
+        else
             (void)hipGetLastError();
-        }
     });
-    return g_dev[dev].ok ? &g_dev[dev] : nullptr;
+    return g_cus[dev];
 }
 
-// Current device of the calling thread, or -1 when there is no usable GPU.
-int current_device() {
-    if (device_count_raw() <= 0) return -1;
-    int d = -1;
-    if (hipGetDevice(&d) != hipSuccess) {
-        (void)hipGetLastError();
-        return -1;
-    }
-    return dev_info(d) ? d : -1;
+int map_err(hipError_t e) {
+    if (e == hipSuccess) return NSX_OK;
+    (void)hipGetLastError();
+    if (e == hipErrorOutOfMemory) return NSX_ENOMEM;
+    if (e == hipErrorNoDevice || e == hipErrorInvalidDevice) return NSX_ENODEV;
+    return NSX_EIO;
 }
-
-int map_err(hipError_t e);
-
-}  // namespace
-
-namespace nsx {
 
 // Launch configuration of one call: the device's CU count + the caller's overrides (nsx_tune.h).
 LaunchCfg launch_cfg(int cus, const nsx_tune* t) {
@@ -89,27 +93,13 @@ LaunchCfg launch_cfg(int cus, const nsx_tune* t) {
 
 }  // namespace nsx
 
-namespace {
-
-nsx::LaunchCfg make_cfg(int dev, const nsx_tune* t) { return nsx::launch_cfg(dev_info(dev)->cus, t); }
-
-int map_err(hipError_t e) {
-    if (e == hipSuccess) return NSX_OK;
-    (void)hipGetLastError();
-    if (e == hipErrorOutOfMemory) return NSX_ENOMEM;
-    if (e == hipErrorNoDevice || e == hipErrorInvalidDevice) return NSX_ENODEV;
-    return NSX_EIO;
-}
-
-}  // namespace
-
 extern "C" {
 
 int nsx_abi_version(void) { return NSX_ABI_VERSION; }
 
 int nsx_device_count(int* out_count) {
     if (!out_count) return NSX_EINVAL;
-    *out_count = device_count_raw();
+    *out_count = nsx::device_count();
     return NSX_OK;
 }
 
@@ -169,35 +159,11 @@ int nsx_ipv4_hdr_launch_count(const void* d_base, uint64_t stride, uint32_t hdr_
     return NSX_OK;
 }
 
-int nsx_csum_ragged_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n,
-                        const uint32_t* d_prefix_partial, uint16_t* d_out, nsx_stream_t stream) {
-    return nsx_csum_ragged_dev_tuned(d_base, d_offsets, n, d_prefix_partial, d_out, stream, nullptr);
-}
-
-int nsx_csum_ragged_dev_tuned(const void* d_base, const uint64_t* d_offsets, uint64_t n,
-                              const uint32_t* d_prefix_partial, uint16_t* d_out, nsx_stream_t stream,
-                              const nsx_tune* tune) {
+// Raw sums (d_raw) and / or per-segment verdicts (d_ok) over ragged segments.
+static int ragged_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n, const uint32_t* d_prefix_partial,
+                      uint8_t* d_ok, uint16_t* d_raw, bool need_raw, nsx_stream_t stream, const nsx_tune* tune) {
     if (n == 0) return NSX_OK;
-    if (!d_out || !d_offsets || !d_base) return NSX_EINVAL;
-    if (n > ((uint64_t)1 << 40)) return NSX_EINVAL;
-    if (!nsx::ragged_tune_valid(nsx::launch_cfg(1, tune))) return NSX_EINVAL;
-    const int dev = current_device();
-    if (dev < 0) return NSX_ENODEV;
-    return map_err(nsx::launch_ragged(make_cfg(dev, tune), d_base, d_offsets, n, d_prefix_partial, d_out, nullptr,
-                                      static_cast<hipStream_t>(stream)));
-}
-
-int nsx_verify_ragged_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n,
-                          const uint32_t* d_prefix_partial, uint8_t* d_ok, uint16_t* d_raw,
-                          nsx_stream_t stream) {
-    return nsx_verify_ragged_dev_tuned(d_base, d_offsets, n, d_prefix_partial, d_ok, d_raw, stream, nullptr);
-}
-
-int nsx_verify_ragged_dev_tuned(const void* d_base, const uint64_t* d_offsets, uint64_t n,
-                                const uint32_t* d_prefix_partial, uint8_t* d_ok, uint16_t* d_raw,
-                                nsx_stream_t stream, const nsx_tune* tune) {
-    if (n == 0) return NSX_OK;
-    if (!d_ok || !d_offsets || !d_base) return NSX_EINVAL;
+    if (!(need_raw ? (void*)d_raw : (void*)d_ok) || !d_offsets || !d_base) return NSX_EINVAL;
     if (n > ((uint64_t)1 << 40)) return NSX_EINVAL;
     if (!nsx::ragged_tune_valid(nsx::launch_cfg(1, tune))) return NSX_EINVAL;
     const int dev = current_device();
@@ -206,246 +172,154 @@ int nsx_verify_ragged_dev_tuned(const void* d_base, const uint64_t* d_offsets, u
                                       static_cast<hipStream_t>(stream)));
 }
 
+int nsx_csum_ragged_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n,
+                        const uint32_t* d_prefix_partial, uint16_t* d_out, nsx_stream_t stream) {
+    return ragged_dev(d_base, d_offsets, n, d_prefix_partial, nullptr, d_out, true, stream, nullptr);
+}
+
+int nsx_csum_ragged_dev_tuned(const void* d_base, const uint64_t* d_offsets, uint64_t n,
+                              const uint32_t* d_prefix_partial, uint16_t* d_out, nsx_stream_t stream,
+                              const nsx_tune* tune) {
+    return ragged_dev(d_base, d_offsets, n, d_prefix_partial, nullptr, d_out, true, stream, tune);
+}
+
+int nsx_verify_ragged_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n,
+                          const uint32_t* d_prefix_partial, uint8_t* d_ok, uint16_t* d_raw,
+                          nsx_stream_t stream) {
+    return ragged_dev(d_base, d_offsets, n, d_prefix_partial, d_ok, d_raw, false, stream, nullptr);
+}
+
+int nsx_verify_ragged_dev_tuned(const void* d_base, const uint64_t* d_offsets, uint64_t n,
+                                const uint32_t* d_prefix_partial, uint8_t* d_ok, uint16_t* d_raw,
+                                nsx_stream_t stream, const nsx_tune* tune) {
+    return ragged_dev(d_base, d_offsets, n, d_prefix_partial, d_ok, d_raw, false, stream, tune);
+}
+
+static int rx_dev(int ipver, const void* d_base, const uint64_t* d_offsets, uint64_t n, uint64_t* d_mask,
+                  uint16_t* d_ip_raw, uint16_t* d_tcp_raw, nsx_stream_t stream, const nsx_tune* tune) {
+    if (n == 0) return NSX_OK;
+    if (!d_base || !d_offsets || !d_mask) return NSX_EINVAL;
+    if (n > ((uint64_t)1 << 40)) return NSX_EINVAL;
+    const int dev = current_device();
+    if (dev < 0) return NSX_ENODEV;
+    const nsx::LaunchCfg cfg = make_cfg(dev, tune);
+    if (!nsx::rx_tune_valid(cfg)) return NSX_EINVAL;
+    return map_err(nsx::launch_rx_tcp(cfg, ipver, d_base, d_offsets, n, d_mask, d_ip_raw, d_tcp_raw,
+                                      static_cast<hipStream_t>(stream)));
+}
+
 int nsx_rx_ipv4_tcp_verify_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n, uint64_t* d_mask,
                                uint16_t* d_ip_raw, uint16_t* d_tcp_raw, nsx_stream_t stream) {
-    return nsx_rx_ipv4_tcp_verify_dev_tuned(d_base, d_offsets, n, d_mask, d_ip_raw, d_tcp_raw, stream, nullptr);
+    return rx_dev(4, d_base, d_offsets, n, d_mask, d_ip_raw, d_tcp_raw, stream, nullptr);
 }
 
 int nsx_rx_ipv4_tcp_verify_dev_tuned(const void* d_base, const uint64_t* d_offsets, uint64_t n, uint64_t* d_mask,
                                      uint16_t* d_ip_raw, uint16_t* d_tcp_raw, nsx_stream_t stream,
                                      const nsx_tune* tune) {
-    if (n == 0) return NSX_OK;
-    if (!d_base || !d_offsets || !d_mask) return NSX_EINVAL;
-    if (n > ((uint64_t)1 << 40)) return NSX_EINVAL;
-    const int dev = current_device();
-    if (dev < 0) return NSX_ENODEV;
-    const nsx::LaunchCfg cfg = make_cfg(dev, tune);
-    if (!nsx::rx_tune_valid(cfg)) return NSX_EINVAL;
-    return map_err(nsx::launch_rx_tcp(cfg, 4, d_base, d_offsets, n, d_mask, d_ip_raw, d_tcp_raw,
-                                      static_cast<hipStream_t>(stream)));
+    return rx_dev(4, d_base, d_offsets, n, d_mask, d_ip_raw, d_tcp_raw, stream, tune);
 }
 
 int nsx_rx_ipv6_tcp_verify_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n, uint64_t* d_mask,
                                uint16_t* d_tcp_raw, nsx_stream_t stream) {
-    return nsx_rx_ipv6_tcp_verify_dev_tuned(d_base, d_offsets, n, d_mask, d_tcp_raw, stream, nullptr);
+    return rx_dev(6, d_base, d_offsets, n, d_mask, nullptr, d_tcp_raw, stream, nullptr);
 }
 
 int nsx_rx_ipv6_tcp_verify_dev_tuned(const void* d_base, const uint64_t* d_offsets, uint64_t n, uint64_t* d_mask,
                                      uint16_t* d_tcp_raw, nsx_stream_t stream, const nsx_tune* tune) {
-    if (n == 0) return NSX_OK;
-    if (!d_base || !d_offsets || !d_mask) return NSX_EINVAL;
-    if (n > ((uint64_t)1 << 40)) return NSX_EINVAL;
-    const int dev = current_device();
-    if (dev < 0) return NSX_ENODEV;
-    const nsx::LaunchCfg cfg = make_cfg(dev, tune);
-    if (!nsx::rx_tune_valid(cfg)) return NSX_EINVAL;
-    return map_err(nsx::launch_rx_tcp(cfg, 6, d_base, d_offsets, n, d_mask, nullptr, d_tcp_raw,
-                                      static_cast<hipStream_t>(stream)));
+    return rx_dev(6, d_base, d_offsets, n, d_mask, nullptr, d_tcp_raw, stream, tune);
 }
 
-int nsx_pseudo_ipv4_partial_dev(const uint8_t* d_src, const uint8_t* d_dst, const uint32_t* d_len,
-                                uint8_t proto, uint64_t n, uint32_t* d_partial, nsx_stream_t stream) {
-    if (n == 0) return NSX_OK;
-    if (!d_src || !d_dst || !d_len || !d_partial) return NSX_EINVAL;
-    const int dev = current_device();
-    if (dev < 0) return NSX_ENODEV;
-    const DevInfo* di = dev_info(dev);
-    return map_err(nsx::launch_pseudo_ipv4(d_src, d_dst, d_len, proto, n, d_partial, (uint32_t)di->cus * 8,
-                                           static_cast<hipStream_t>(stream)));
-}
-
-int nsx_pseudo_ipv6_partial_dev(const uint8_t* d_src, const uint8_t* d_dst, const uint32_t* d_len,
-                                uint8_t next_header, uint64_t n, uint32_t* d_partial, nsx_stream_t stream) {
-    if (n == 0) return NSX_OK;
-    if (!d_src || !d_dst || !d_len || !d_partial) return NSX_EINVAL;
-    const int dev = current_device();
-    if (dev < 0) return NSX_ENODEV;
-    const DevInfo* di = dev_info(dev);
-    return map_err(nsx::launch_pseudo_ipv6(d_src, d_dst, d_len, next_header, n, d_partial, (uint32_t)di->cus * 8,
-                                           static_cast<hipStream_t>(stream)));
-}
+#define NSX_PSEUDO_DEV(V)                                                                                        \
+    int nsx_pseudo_ipv##V##_partial_dev(const uint8_t* d_src, const uint8_t* d_dst, const uint32_t* d_len,       \
+                                        uint8_t proto, uint64_t n, uint32_t* d_partial, nsx_stream_t stream) {   \
+        if (n == 0) return NSX_OK;                                                                               \
+        if (!d_src || !d_dst || !d_len || !d_partial) return NSX_EINVAL;                                         \
+        const int dev = current_device();                                                                        \
+        if (dev < 0) return NSX_ENODEV;                                                                          \
+        return map_err(nsx::launch_pseudo_ipv##V(d_src, d_dst, d_len, proto, n, d_partial, aux_blocks(dev),      \
+                                                 static_cast<hipStream_t>(stream)));                             \
+    }
+NSX_PSEUDO_DEV(4)  // proto: the protocol byte
+NSX_PSEUDO_DEV(6)  // proto: the next-header byte
+#undef NSX_PSEUDO_DEV
 
 int nsx_verify_mask_dev(const uint16_t* d_raw, uint64_t n, uint64_t* d_mask, nsx_stream_t stream) {
     if (n == 0) return NSX_OK;
     if (!d_raw || !d_mask) return NSX_EINVAL;
     const int dev = current_device();
     if (dev < 0) return NSX_ENODEV;
-    const DevInfo* di = dev_info(dev);
-    return map_err(nsx::launch_verify_mask(d_raw, n, d_mask, (uint32_t)di->cus * 8, static_cast<hipStream_t>(stream)));
+    return map_err(nsx::launch_verify_mask(d_raw, n, d_mask, aux_blocks(dev), static_cast<hipStream_t>(stream)));
 }
 
-uint64_t nsx_tcp_wire_len(uint64_t opt_len, uint64_t data_len) {
-    return 20u + opt_len + (opt_len ? (20u + opt_len) % 4u : 0u) + data_len;
-}
-
-int nsx_tcp_layout_host(const uint64_t* h_opt_off, const uint64_t* h_data_off, uint64_t n, uint64_t* h_out_off) {
-    if (!h_out_off || (n && !h_data_off)) return NSX_EINVAL;
-    uint64_t at = 0;
-    for (uint64_t i = 0; i < n; ++i) {
-        h_out_off[i] = at;
-        const uint64_t ol = h_opt_off ? h_opt_off[i + 1] - h_opt_off[i] : 0;
-        at += (nsx_tcp_wire_len(ol, h_data_off[i + 1] - h_data_off[i]) + 3) & ~3ull;
-    }
-    h_out_off[n] = at;
-    return NSX_OK;
+// nsx_tcp_wire_len and the *_layout_host / nsx_tso_count_host calls need no device: host_plan.cpp.
+// The sender pass (ipver 0: TCP images over partials) and the fused transmit pass (ipver 4 / 6: the IP fields too).
+static int build_dev(int ipver, const nsx_ip_hdr_soa* ip, const nsx_tcp_hdr_soa* hdr, const uint8_t* d_opts,
+                     const uint64_t* d_opt_off, const uint8_t* d_data, const uint64_t* d_data_off, uint64_t data_bytes,
+                     const uint32_t* d_partial, uint64_t n, uint8_t* d_out, const uint64_t* d_out_off, uint16_t* d_raw,
+                     nsx_stream_t stream, const nsx_tune* tune) {
+    if (n == 0) return NSX_OK;
+    if ((ipver && !nsx::ip_hdr_ok(ip)) || !nsx::tcp_hdr_ok(hdr) || !d_data_off || !d_out || !d_out_off ||
+        (d_opt_off && !d_opts) || (data_bytes && !d_data))
+        return NSX_EINVAL;
+    const int dev = current_device();
+    if (dev < 0) return NSX_ENODEV;
+    const nsx::IpHdrSoA a = ipver ? to_soa(*ip) : nsx::IpHdrSoA{};
+    return map_err(nsx::launch_tcp_build(make_cfg(dev, tune), ipver, ipver ? &a : nullptr, to_soa(*hdr), d_opts,
+                                         d_opt_off, d_data, d_data_off, data_bytes, d_partial, n, d_out, d_out_off,
+                                         d_raw, static_cast<hipStream_t>(stream)));
 }
 
 int nsx_tcp_build_dev(const nsx_tcp_hdr_soa* hdr, const uint8_t* d_opts, const uint64_t* d_opt_off,
                       const uint8_t* d_data, const uint64_t* d_data_off, uint64_t data_bytes,
                       const uint32_t* d_prefix_partial, uint64_t n, uint8_t* d_out, const uint64_t* d_out_off,
                       uint16_t* d_raw, nsx_stream_t stream) {
-    return nsx_tcp_build_dev_tuned(hdr, d_opts, d_opt_off, d_data, d_data_off, data_bytes, d_prefix_partial, n, d_out,
-                                   d_out_off, d_raw, stream, nullptr);
+    return build_dev(0, nullptr, hdr, d_opts, d_opt_off, d_data, d_data_off, data_bytes, d_prefix_partial, n, d_out,
+                     d_out_off, d_raw, stream, nullptr);
 }
 
 int nsx_tcp_build_dev_tuned(const nsx_tcp_hdr_soa* hdr, const uint8_t* d_opts, const uint64_t* d_opt_off,
                             const uint8_t* d_data, const uint64_t* d_data_off, uint64_t data_bytes,
                             const uint32_t* d_prefix_partial, uint64_t n, uint8_t* d_out, const uint64_t* d_out_off,
                             uint16_t* d_raw, nsx_stream_t stream, const nsx_tune* tune) {
-    if (n == 0) return NSX_OK;
-    if (!hdr || !hdr->src_port || !hdr->dst_port || !hdr->seq_num || !hdr->ack_num ||
-        !hdr->control || !hdr->window || !hdr->urgent_ptr || !d_data_off || !d_out || !d_out_off ||
-        (d_opt_off && !d_opts) || (data_bytes && !d_data))
-        return NSX_EINVAL;
-    const int dev = current_device();
-    if (dev < 0) return NSX_ENODEV;
-    const nsx::TcpHdrSoA h{hdr->src_port, hdr->dst_port, hdr->seq_num, hdr->ack_num,
-                           hdr->offset,   hdr->control,  hdr->window,  hdr->urgent_ptr};
-    return map_err(nsx::launch_tcp_build(make_cfg(dev, tune), 0, nullptr, h, d_opts, d_opt_off, d_data, d_data_off,
-                                         data_bytes, d_prefix_partial, n, d_out, d_out_off, d_raw,
-                                         static_cast<hipStream_t>(stream)));
+    return build_dev(0, nullptr, hdr, d_opts, d_opt_off, d_data, d_data_off, data_bytes, d_prefix_partial, n, d_out,
+                     d_out_off, d_raw, stream, tune);
 }
 
-int nsx_tx_layout_host(const uint64_t* h_opt_off, const uint64_t* h_data_off, uint64_t n, uint32_t ip_hdr_len,
-                       uint64_t* h_out_off) {
-    if ((ip_hdr_len != 20 && ip_hdr_len != 40) || !h_out_off || (n && !h_data_off)) return NSX_EINVAL;
-    uint64_t at = 0;
-    for (uint64_t i = 0; i < n; ++i) {
-        h_out_off[i] = at;
-        const uint64_t ol = h_opt_off ? h_opt_off[i + 1] - h_opt_off[i] : 0;
-        at += (ip_hdr_len + nsx_tcp_wire_len(ol, h_data_off[i + 1] - h_data_off[i]) + 3) & ~3ull;
+#define NSX_TX_DEV(V)                                                                                             \
+    int nsx_tx_ipv##V##_tcp_build_dev(const nsx_ip_hdr_soa* ip, const nsx_tcp_hdr_soa* tcp, const uint8_t* d_opts, \
+                                      const uint64_t* d_opt_off, const uint8_t* d_data, const uint64_t* d_data_off, \
+                                      uint64_t data_bytes, uint64_t n, uint8_t* d_out, const uint64_t* d_out_off, \
+                                      uint16_t* d_tcp_raw, nsx_stream_t stream) {                                 \
+        return build_dev(V, ip, tcp, d_opts, d_opt_off, d_data, d_data_off, data_bytes, nullptr, n, d_out,        \
+                         d_out_off, d_tcp_raw, stream, nullptr);                                                  \
+    }                                                                                                             \
+    int nsx_tx_ipv##V##_tcp_build_dev_tuned(                                                                      \
+        const nsx_ip_hdr_soa* ip, const nsx_tcp_hdr_soa* tcp, const uint8_t* d_opts, const uint64_t* d_opt_off,   \
+        const uint8_t* d_data, const uint64_t* d_data_off, uint64_t data_bytes, uint64_t n, uint8_t* d_out,       \
+        const uint64_t* d_out_off, uint16_t* d_tcp_raw, nsx_stream_t stream, const nsx_tune* tune) {              \
+        return build_dev(V, ip, tcp, d_opts, d_opt_off, d_data, d_data_off, data_bytes, nullptr, n, d_out,        \
+                         d_out_off, d_tcp_raw, stream, tune);                                                     \
     }
-    h_out_off[n] = at;
-    return NSX_OK;
-}
+NSX_TX_DEV(4)
+NSX_TX_DEV(6)
+#undef NSX_TX_DEV
 
-// The fused transmit pass: nsx_tcp_build_dev's validation plus the IP fields', then the same launcher.
-static int tx_build_dev(int ipver, const nsx_ip_hdr_soa* ip, const nsx_tcp_hdr_soa* hdr, const uint8_t* d_opts,
-                        const uint64_t* d_opt_off, const uint8_t* d_data, const uint64_t* d_data_off,
-                        uint64_t data_bytes, uint64_t n, uint8_t* d_out, const uint64_t* d_out_off,
-                        uint16_t* d_tcp_raw, nsx_stream_t stream, const nsx_tune* tune) {
-    if (n == 0) return NSX_OK;
-    if (!ip || !ip->src || !ip->dst || !hdr || !hdr->src_port || !hdr->dst_port || !hdr->seq_num || !hdr->ack_num ||
-        !hdr->control || !hdr->window || !hdr->urgent_ptr || !d_data_off || !d_out || !d_out_off ||
-        (d_opt_off && !d_opts) || (data_bytes && !d_data))
-        return NSX_EINVAL;
-    const int dev = current_device();
-    if (dev < 0) return NSX_ENODEV;
-    const nsx::IpHdrSoA a{ip->src, ip->dst, ip->ident, ip->ttl, ip->tclass, ip->flow};
-    const nsx::TcpHdrSoA h{hdr->src_port, hdr->dst_port, hdr->seq_num, hdr->ack_num,
-                           hdr->offset,   hdr->control,  hdr->window,  hdr->urgent_ptr};
-    return map_err(nsx::launch_tcp_build(make_cfg(dev, tune), ipver, &a, h, d_opts, d_opt_off, d_data, d_data_off,
-                                         data_bytes, nullptr, n, d_out, d_out_off, d_tcp_raw,
-                                         static_cast<hipStream_t>(stream)));
-}
-
-int nsx_tx_ipv4_tcp_build_dev(const nsx_ip_hdr_soa* ip, const nsx_tcp_hdr_soa* tcp, const uint8_t* d_opts,
-                              const uint64_t* d_opt_off, const uint8_t* d_data, const uint64_t* d_data_off,
-                              uint64_t data_bytes, uint64_t n, uint8_t* d_out, const uint64_t* d_out_off,
-                              uint16_t* d_tcp_raw, nsx_stream_t stream) {
-    return tx_build_dev(4, ip, tcp, d_opts, d_opt_off, d_data, d_data_off, data_bytes, n, d_out, d_out_off, d_tcp_raw,
-                        stream, nullptr);
-}
-
-int nsx_tx_ipv4_tcp_build_dev_tuned(const nsx_ip_hdr_soa* ip, const nsx_tcp_hdr_soa* tcp, const uint8_t* d_opts,
-                                    const uint64_t* d_opt_off, const uint8_t* d_data, const uint64_t* d_data_off,
-                                    uint64_t data_bytes, uint64_t n, uint8_t* d_out, const uint64_t* d_out_off,
-                                    uint16_t* d_tcp_raw, nsx_stream_t stream, const nsx_tune* tune) {
-    return tx_build_dev(4, ip, tcp, d_opts, d_opt_off, d_data, d_data_off, data_bytes, n, d_out, d_out_off, d_tcp_raw,
-                        stream, tune);
-}
-
-int nsx_tx_ipv6_tcp_build_dev(const nsx_ip_hdr_soa* ip, const nsx_tcp_hdr_soa* tcp, const uint8_t* d_opts,
-                              const uint64_t* d_opt_off, const uint8_t* d_data, const uint64_t* d_data_off,
-                              uint64_t data_bytes, uint64_t n, uint8_t* d_out, const uint64_t* d_out_off,
-                              uint16_t* d_tcp_raw, nsx_stream_t stream) {
-    return tx_build_dev(6, ip, tcp, d_opts, d_opt_off, d_data, d_data_off, data_bytes, n, d_out, d_out_off, d_tcp_raw,
-                        stream, nullptr);
-}
-
-int nsx_tx_ipv6_tcp_build_dev_tuned(const nsx_ip_hdr_soa* ip, const nsx_tcp_hdr_soa* tcp, const uint8_t* d_opts,
-                                    const uint64_t* d_opt_off, const uint8_t* d_data, const uint64_t* d_data_off,
-                                    uint64_t data_bytes, uint64_t n, uint8_t* d_out, const uint64_t* d_out_off,
-                                    uint16_t* d_tcp_raw, nsx_stream_t stream, const nsx_tune* tune) {
-    return tx_build_dev(6, ip, tcp, d_opts, d_opt_off, d_data, d_data_off, data_bytes, n, d_out, d_out_off, d_tcp_raw,
-                        stream, tune);
-}
-
-// ---- segmentation offload: the frame map on the host, then the transmit pass's launcher over super-segments ----
-// Frames of super-segment i: max(1, ceil(len / mss)).
-static uint64_t tso_frames(uint64_t len, uint32_t mss) { return len ? (len + mss - 1) / mss : 1; }
-
-int nsx_tso_count_host(const uint64_t* h_data_off, const uint32_t* h_mss, uint64_t n, uint64_t* h_frame_first) {
-    if (!h_frame_first || n >= (1ull << 32) || (n && (!h_data_off || !h_mss))) return NSX_EINVAL;
-    uint64_t at = 0;
-    for (uint64_t i = 0; i < n; ++i) {
-        if (h_mss[i] == 0 || h_data_off[i + 1] < h_data_off[i]) return NSX_EINVAL;
-        h_frame_first[i] = at;
-        at += tso_frames(h_data_off[i + 1] - h_data_off[i], h_mss[i]);
-    }
-    h_frame_first[n] = at;
-    return NSX_OK;
-}
-
-int nsx_tso_layout_host(const uint64_t* h_opt_off, const uint64_t* h_data_off, const uint32_t* h_mss,
-                        const uint64_t* h_frame_first, uint64_t n, uint32_t ip_hdr_len, uint32_t* h_frame_seg,
-                        uint64_t* h_out_off) {
-    if ((ip_hdr_len != 20 && ip_hdr_len != 40) || !h_out_off || !h_frame_first || n >= (1ull << 32) ||
-        (n && (!h_data_off || !h_mss)))
-        return NSX_EINVAL;
-    uint64_t f = 0;
-    for (uint64_t i = 0; i < n; ++i) {  // everything checked before anything is written
-        if (h_mss[i] == 0 || h_data_off[i + 1] < h_data_off[i] || (h_opt_off && h_opt_off[i + 1] < h_opt_off[i]) ||
-            h_frame_first[i] != f)
-            return NSX_EINVAL;
-        f += tso_frames(h_data_off[i + 1] - h_data_off[i], h_mss[i]);
-    }
-    if (h_frame_first[n] != f || (f && !h_frame_seg)) return NSX_EINVAL;
-    uint64_t at = 0;
-    f = 0;
-    for (uint64_t i = 0; i < n; ++i) {
-        const uint64_t ol = h_opt_off ? h_opt_off[i + 1] - h_opt_off[i] : 0;
-        const uint64_t len = h_data_off[i + 1] - h_data_off[i], cnt = tso_frames(len, h_mss[i]);
-        for (uint64_t j = 0; j < cnt; ++j, ++f) {
-            const uint64_t dl = std::min<uint64_t>(h_mss[i], len - j * h_mss[i]);
-            h_frame_seg[f] = (uint32_t)i;
-            h_out_off[f] = at;
-            at += (ip_hdr_len + nsx_tcp_wire_len(ol, dl) + 3) & ~3ull;
-        }
-    }
-    h_out_off[f] = at;
-    return NSX_OK;
-}
-
+// ---- segmentation offload: the transmit pass's launcher over super-segments (the frame map: host_plan.cpp) ----
 static int tso_build_dev(int ipver, const nsx_ip_hdr_soa* ip, const nsx_tcp_hdr_soa* hdr, const uint8_t* d_opts,
                          const uint64_t* d_opt_off, const uint8_t* d_data, const uint64_t* d_data_off,
                          uint64_t data_bytes, const uint32_t* d_mss, uint64_t n, const uint64_t* d_frame_first,
                          const uint32_t* d_frame_seg, uint64_t n_frames, uint8_t* d_out, const uint64_t* d_out_off,
                          uint16_t* d_tcp_raw, nsx_stream_t stream, const nsx_tune* tune) {
     if (n_frames == 0) return NSX_OK;
-    if (n == 0 || n >= (1ull << 32) || n_frames < n || !ip || !ip->src || !ip->dst || !hdr || !hdr->src_port ||
-        !hdr->dst_port || !hdr->seq_num || !hdr->ack_num || !hdr->control || !hdr->window || !hdr->urgent_ptr ||
-        !d_data_off || !d_mss || !d_frame_first || !d_frame_seg || !d_out || !d_out_off || (d_opt_off && !d_opts) ||
+    if (n == 0 || n >= (1ull << 32) || n_frames < n || !nsx::ip_hdr_ok(ip) || !nsx::tcp_hdr_ok(hdr) || !d_data_off ||
+        !d_mss || !d_frame_first || !d_frame_seg || !d_out || !d_out_off || (d_opt_off && !d_opts) ||
         (data_bytes && !d_data))
         return NSX_EINVAL;
     const int dev = current_device();
     if (dev < 0) return NSX_ENODEV;
-    const nsx::IpHdrSoA a{ip->src, ip->dst, ip->ident, ip->ttl, ip->tclass, ip->flow};
     const nsx::TsoMap m{d_mss, d_frame_first, d_frame_seg};
-    const nsx::TcpHdrSoA h{hdr->src_port, hdr->dst_port, hdr->seq_num, hdr->ack_num,
-                           hdr->offset,   hdr->control,  hdr->window,  hdr->urgent_ptr};
-    return map_err(nsx::launch_tso_build(make_cfg(dev, tune), ipver, a, m, h, d_opts, d_opt_off, d_data, d_data_off,
-                                         data_bytes, n_frames, d_out, d_out_off, d_tcp_raw,
+    return map_err(nsx::launch_tso_build(make_cfg(dev, tune), ipver, to_soa(*ip), m, to_soa(*hdr), d_opts, d_opt_off,
+                                         d_data, d_data_off, data_bytes, n_frames, d_out, d_out_off, d_tcp_raw,
                                          static_cast<hipStream_t>(stream)));
 }
 
@@ -500,10 +374,7 @@ static int gro_dev(int ipver, bool flow, const void* d_base, const uint64_t* d_o
     if (work_bytes < (flow ? nsx::gro_flow_work_bytes(n) : nsx::gro_work_bytes(n))) return NSX_EINVAL;
     const int dev = current_device();
     if (dev < 0) return NSX_ENODEV;
-    const nsx::GroOut g{o->n_super, o->src,      o->dst,         o->ident,     o->ttl,     o->tclass,
-                        o->flow,    o->src_port, o->dst_port,    o->seq_num,   o->ack_num, o->offset,
-                        o->control, o->window,   o->urgent_ptr,  o->mss,       o->opts,    o->opt_off,
-                        o->data,    o->data_off, o->first_frame, o->frame_cnt, o->frame_seg};
+    const nsx::GroOut g = to_soa(*o);
     if (flow)
         return map_err(nsx::launch_gro_flow(make_cfg(dev, tune), ipver, d_base, d_offsets, n, d_valid, d_order, g,
                                             d_work, static_cast<hipStream_t>(stream)));
@@ -542,10 +413,7 @@ int nsx_tcp_parse_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n,
     if (!d_base || !d_offsets || !out) return NSX_EINVAL;
     const int dev = current_device();
     if (dev < 0) return NSX_ENODEV;
-    const nsx::TcpParsedSoA o{out->src_port, out->dst_port, out->seq_num,    out->ack_num,
-                              out->offset,   out->control,  out->window,     out->checksum,
-                              out->urgent_ptr, out->data_off, out->n_options, out->status};
-    return map_err(nsx::launch_tcp_parse(make_cfg(dev, nullptr), d_base, d_offsets, n, o,
+    return map_err(nsx::launch_tcp_parse(make_cfg(dev, nullptr), d_base, d_offsets, n, to_soa(*out),
                                          static_cast<hipStream_t>(stream)));
 }
 
@@ -595,8 +463,7 @@ int nsx_fill_splitmix64_dev(void* d_buf, uint64_t byte_off, uint64_t nbytes, uin
     if (!d_buf) return NSX_EINVAL;
     const int dev = current_device();
     if (dev < 0) return NSX_ENODEV;
-    const DevInfo* di = dev_info(dev);
-    return map_err(nsx::launch_fill_splitmix64(d_buf, byte_off, nbytes, seed, (uint32_t)di->cus * 8,
+    return map_err(nsx::launch_fill_splitmix64(d_buf, byte_off, nbytes, seed, aux_blocks(dev),
                                                static_cast<hipStream_t>(stream)));
 }
 
@@ -626,7 +493,7 @@ int nsx_alloc_pinned(size_t bytes, void** out) {
     if (!out) return NSX_EINVAL;
     *out = nullptr;
     if (bytes == 0) return NSX_OK;
-    if (device_count_raw() <= 0) return NSX_ENODEV;
+    if (nsx::device_count() <= 0) return NSX_ENODEV;
     hipError_t e = hipHostMalloc(out, bytes, hipHostMallocPortable);
     if (e != hipSuccess) {
         *out = nullptr;

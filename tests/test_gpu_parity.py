@@ -664,14 +664,49 @@ def test_host_batch_more_gpus_than_present_is_enodev():
     assert np.array_equal(nsx.fixed_host(buf, 1500, 1500, 2, num_gpus=nsx.device_count()), [0, 0])
 
 
-def _host_build_case(rng, n, with_opts, lead=7):
-    """Host-resident sender batch: payloads of 0-1600 B (every 97th a 8940 B jumbo payload) packed behind `lead`
-    bytes, random header fields, every third segment (with_opts) carrying one of _OPT_SETS' option lists, and each
-    segment's own IPv4 pseudo-header (TCP length = its wire length). Returns (fields, data, data_off, opts,
-    opt_off, pseudo, partials)."""
+@pytest.mark.parametrize("shards", [1, 3])
+@pytest.mark.parametrize("mem", ["pageable", "pinned"])
+def test_host_batch_small_chunks(mem, shards):
+    """nsx_tune.chunk_bytes on the checksum host calls: a 4096 B budget cuts small batches into many chunks, so both
+    stream slots of a shard are reused. Fixed stride: 37 segments of 1500 B every 1503 B (two per chunk) and of 5000 B
+    (overlapping, each a chunk of its own) in a view 3 bytes into its buffer, and a single segment (one chunk, one
+    slot). Ragged: 41 segments cycling through 0, 1, 63, 64, 1500 and 9000 B from offset 1 — the 9000 B ones chunks
+    of their own, empty ones on chunk edges. With partials, pageable or pinned, against the oracle; the same batches
+    in one chunk (no budget) too."""
+    rng = np.random.default_rng(0xC0 + shards)
+    stride = 1503
+    lens = np.array([0, 1, 63, 64, 1500, 9000] * 7, np.uint64)[:41]
+    offs = np.zeros(lens.size + 1, np.uint64)
+    offs[1:] = np.cumsum(lens)
+    offs += np.uint64(1)
+    size = max(3 + 36 * stride + 5000, int(offs[-1]) + 2)
+    pin = nsx.PinnedBuffer(size) if mem == "pinned" else None
+    buf = pin.array if pin is not None else np.empty(size, np.uint8)
+    buf[:] = rng.integers(0, 256, size, dtype=np.uint8)
+    for chunk in (4096, 0):
+        tune = dict(shards_per_device=shards, chunk_bytes=chunk)
+        for n, seg_len in ((37, 1500), (37, 5000), (1, 1500)):
+            part = rng.integers(0, 1 << 20, n, dtype=np.uint64).astype(np.uint32)
+            got = nsx.fixed_host(buf[3:], stride, seg_len, n, partial=part, tune=tune)
+            want = O.c_batch(buf[3:], n, stride=stride, seg_len=seg_len, partial=part)
+            assert np.array_equal(got, want), (chunk, n, seg_len)
+        part = rng.integers(0, 1 << 20, lens.size, dtype=np.uint64).astype(np.uint32)
+        got = nsx.ragged_host(buf, offs, partial=part, tune=tune)
+        assert np.array_equal(got, O.c_batch(buf, lens.size, offsets=offs, partial=part)), chunk
+    if pin is not None:
+        pin.free()
+
+
+def _host_build_case(rng, n, with_opts, lead=7, jumbo_at=None):
+    """Host-resident sender batch: payloads of 0-1600 B (every 97th, and segment `jumbo_at`, a 8940 B jumbo payload)
+    packed behind `lead` bytes, random header fields, every third segment (with_opts) carrying one of _OPT_SETS'
+    option lists, and each segment's own IPv4 pseudo-header (TCP length = its wire length). Returns (fields, data,
+    data_off, opts, opt_off, pseudo, partials)."""
     lens = rng.integers(0, 1601, n).astype(np.uint64)
     lens[::97] = 8940
     lens[:3] = [0, 1, 1480][:n]
+    if jumbo_at is not None:
+        lens[jumbo_at] = 8940
     data = rng.integers(0, 256, lead + int(lens.sum()) + 8, dtype=np.uint8)
     data_off = np.zeros(n + 1, np.uint64)
     data_off[1:] = np.cumsum(lens)
@@ -786,6 +821,71 @@ def test_tcp_build_host_gaps_offset_none_no_raw_and_the_device_call():
     wwant, wwraw = O.c_go_tcp_build_mt(fw, dw, doff, np.arange(m + 1, dtype=np.uint64) * np.uint64(W), ps)
     gw, rw = nsx.tcp_build_host(fw, dw, doff, partial=pp, tune=dict(shards_per_device=2))
     assert np.array_equal(rw, wwraw) and np.array_equal(gw, wwant)
+
+
+@pytest.mark.parametrize("shards", [1, 3])
+@pytest.mark.parametrize("mem", ["pageable", "pinned"])
+def test_tcp_build_host_small_chunks(mem, shards):
+    """nsx_tcp_build_host cut into 2048 B chunks (nsx_tune.chunk_bytes): 50 segments, options on every third,
+    payloads of 0, 1 and 8940 B among them — ~30 chunks on one shard, the jumbo segment a chunk of its own. Packed,
+    and with 4-byte-multiple gaps over a sentinel-filled output whose bytes between the padded images must survive;
+    with and without raw sums; and once in a single chunk. Every image byte, gap byte and raw sum against the
+    Go-faithful sender loop (O.c_go_tcp_build_mt)."""
+    rng = np.random.default_rng(0xD0)
+    n = 50
+    fields, data, data_off, ob, oo, pseudo, part = _host_build_case(rng, n, True, jumbo_at=31)
+    lens = np.diff(data_off)
+    assert {0, 1, 8940} <= set(lens.tolist())
+    packed = nsx.tcp_layout_host(data_off, oo)
+    slot = np.diff(packed)
+    gap = 4 * rng.integers(0, 9, n).astype(np.uint64) * (rng.random(n) < 0.3)
+    wide = np.zeros(n + 1, np.uint64)
+    wide[1:] = np.cumsum(slot + gap)
+    assert gap.any()
+    dp = nsx.PinnedBuffer(data.nbytes) if mem == "pinned" else None
+    if dp is not None:
+        dp.array[:] = data
+    for off in (packed, wide):
+        want, wraw = O.c_go_tcp_build_mt(fields, data, data_off, off, pseudo, opts=ob, opt_off=oo)
+        exp = np.full(int(off[-1]), 0xAB, np.uint8)
+        for i in range(n):
+            o = int(off[i])
+            exp[o:o + int(slot[i])] = want[o:o + int(slot[i])]
+        op = nsx.PinnedBuffer(int(off[-1])) if mem == "pinned" else None
+        for want_raw, chunk in ((True, 2048), (False, 2048), (True, 0)):
+            out = op.array if op is not None else np.empty(int(off[-1]), np.uint8)
+            out[:] = 0xAB
+            got, raw = nsx.tcp_build_host(fields, data if dp is None else dp.array, data_off, out_off=off, opts=ob,
+                                          opt_off=oo, partial=part, out=out, want_raw=want_raw,
+                                          tune=dict(shards_per_device=shards, chunk_bytes=chunk))
+            assert np.array_equal(raw, wraw) if want_raw else raw is None, (want_raw, chunk)
+            assert np.array_equal(got, exp), (want_raw, chunk, np.nonzero(got != exp)[0][:8])
+        if op is not None:
+            op.free()
+    if dp is not None:
+        dp.free()
+
+
+def test_host_cache_release_after_small_chunk_calls():
+    """nsx_host_cache_release after the chunked calls above returns 0, and one multi-chunk call of each job kind —
+    fixed, ragged, receive, sender — is exact again on the regrown buffers."""
+    import _rx
+    assert nsx.lib().nsx_host_cache_release() == 0
+    rng = np.random.default_rng(0xD8)
+    tune = dict(chunk_bytes=4096)
+    buf = rng.integers(0, 256, 37 * 1503, dtype=np.uint8)
+    assert np.array_equal(nsx.fixed_host(buf, 1503, 1500, 37, tune=tune), O.c_batch(buf, 37, stride=1503, seg_len=1500))
+    offs = np.zeros(42, np.uint64)
+    offs[1:] = np.cumsum(rng.integers(0, 1300, 41))
+    assert np.array_equal(nsx.ragged_host(buf, offs, tune=tune), O.c_batch(buf, 41, offsets=offs))
+    fbuf, foffs, _ = _rx.batch(rng, 64 * 3 + 5, lead=0, max_payload=1460)
+    assert np.array_equal(nsx.rx_ipv4_tcp_verify_host(fbuf, foffs, tune=tune), O.c_rx_ipv4_tcp(fbuf, foffs)[0])
+    fields, data, data_off, ob, oo, pseudo, part = _host_build_case(rng, 20, True)
+    off = nsx.tcp_layout_host(data_off, oo)
+    want, wraw = O.c_go_tcp_build_mt(fields, data, data_off, off, pseudo, opts=ob, opt_off=oo)
+    got, raw = nsx.tcp_build_host(fields, data, data_off, out_off=off, opts=ob, opt_off=oo, partial=part, tune=tune)
+    assert np.array_equal(raw, wraw) and np.array_equal(got, want)
+    assert nsx.lib().nsx_host_cache_release() == 0
 
 
 def test_tcp_build_host_more_gpus_than_present_is_enodev():

@@ -500,6 +500,34 @@ def test_rx6_host_batches_sharded(shards):
     assert np.array_equal(got, want), shards
 
 
+@pytest.mark.parametrize("shards", [1, 3])
+@pytest.mark.parametrize("mem", ["pageable", "pinned"])
+@pytest.mark.parametrize("ipver", [4, 6])
+def test_rx_host_small_chunks_of_one_mask_word(ipver, mem, shards):
+    """nsx_tune.chunk_bytes on the receive host calls: 64 * 5 + 7 mixed valid / corrupted frames with a 2048 B
+    budget, below every 64 frames' bytes, so each chunk is exactly one mask word (the floor of the 64-frame chunk
+    alignment) and the last is partial; on one shard both stream slots are reused. The mask equals the device
+    call's over the same frames and the oracle's verdicts; a single-chunk call (no budget) does too."""
+    rng = np.random.default_rng(0xA0 + ipver)
+    n = 64 * 5 + 7
+    kinds, payload = (_rx.KINDS6, 1440) if ipver == 6 else (_rx.KINDS, 1460)
+    buf, offs, _ = _rx.batch(rng, n, kinds=kinds, lead=0, max_payload=payload, ip=ipver)
+    assert all(int(offs[min(n, k + 64)] - offs[k]) > 2048 for k in range(0, n - 7, 64))
+    want = (O.c_rx_ipv6_tcp if ipver == 6 else O.c_rx_ipv4_tcp)(buf, offs)[0]
+    assert np.array_equal((run_rx6 if ipver == 6 else run_rx)(buf, offs)[0], want)
+    fn = nsx.rx_ipv6_tcp_verify_host if ipver == 6 else nsx.rx_ipv4_tcp_verify_host
+    pin = None
+    if mem == "pinned":
+        pin = nsx.PinnedBuffer(buf.nbytes)
+        pin.array[:] = buf
+        buf = pin.array
+    got = fn(buf, offs, tune=dict(shards_per_device=shards, chunk_bytes=2048))
+    one = fn(buf, offs, tune=dict(shards_per_device=shards))
+    if pin is not None:
+        pin.free()
+    assert np.array_equal(got, want) and np.array_equal(one, want)
+
+
 @pytest.mark.parametrize("ipver", [4, 6])
 def test_rx_parked_raw_sums_any_output_alignment(ipver):
     """The streamed form parks its raw sums in the wave's LDS slot and writes them in 16 B

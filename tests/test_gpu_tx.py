@@ -302,6 +302,53 @@ def test_tx_host_calls(ipver, mem, shards):
     assert np.array_equal(got, dgot) and np.array_equal(raw, draw)
 
 
+@functools.lru_cache(maxsize=None)
+def _small_host_case(ipver):
+    """50 frames, options on every third: payloads of 0-1600 B with a 0, a 1 and a 8940 B one among them; packed
+    slots, and slots with 4-byte-multiple gaps. Expected frames over an 0xAB-filled buffer for both."""
+    rng = np.random.default_rng(0x110 + ipver)
+    n = 50
+    lens = rng.integers(0, 1601, n)
+    lens[[0, 1, 2, 31]] = [0, 1, 1480, 8940]
+    c = _tx.Case(rng, ipver, lens, opts=_opt_list(rng, n), lead=7)
+    packed = c.packed()
+    gap = 4 * rng.integers(0, 9, n).astype(np.uint64) * (rng.random(n) < 0.3)
+    wide = np.zeros(n + 1, np.uint64)
+    wide[1:] = np.cumsum(np.diff(packed) + gap)
+    assert gap.any()
+    return c, [(off, *_tx.expected(c, off, fill=0xAB)) for off in (packed, wide)]
+
+
+@pytest.mark.parametrize("shards", [1, 3])
+@pytest.mark.parametrize("mem", ["pageable", "pinned"])
+@pytest.mark.parametrize("ipver", [4, 6])
+def test_tx_host_calls_small_chunks(ipver, mem, shards):
+    """The transmit host calls cut into 2048 B chunks (nsx_tune.chunk_bytes): ~30 chunks on one shard, so both stream
+    slots are reused many times, the jumbo frame a chunk of its own; packed and gapped layouts over a sentinel-filled
+    output, with and without raw sums, and once in a single chunk. Every frame byte, gap byte and raw sum against
+    tests/_tx.py."""
+    c, layouts = _small_host_case(ipver)
+    fn = nsx.tx_ipv4_tcp_build_host if ipver == 4 else nsx.tx_ipv6_tcp_build_host
+    dp = nsx.PinnedBuffer(c.data.nbytes) if mem == "pinned" else None
+    data = c.data
+    if dp is not None:
+        dp.array[:] = c.data
+        data = dp.array
+    for off, want, wraw in layouts:
+        op = nsx.PinnedBuffer(int(off[-1])) if mem == "pinned" else None
+        for want_raw, chunk in ((True, 2048), (False, 2048), (True, 0)):
+            out = op.array if op is not None else np.empty(int(off[-1]), np.uint8)
+            out[:] = 0xAB
+            got, raw = fn(c.ip, c.fields, data, c.data_off, out_off=off, opts=c.opts, opt_off=c.opt_off, out=out,
+                          want_raw=want_raw, tune=dict(shards_per_device=shards, chunk_bytes=chunk))
+            assert (raw is not None) == want_raw
+            _same(c, off, got.copy(), raw, want, wraw)
+        if op is not None:
+            op.free()
+    if dp is not None:
+        dp.free()
+
+
 @pytest.mark.parametrize("ipver", [4, 6])
 def test_tx_host_more_gpus_than_present_is_enodev(ipver):
     rng = np.random.default_rng(0x104 + ipver)
