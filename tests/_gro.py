@@ -239,6 +239,14 @@ def cut_batch(ipver, mss, opts, lead=0, seed=0):
     return b
 
 
+def cycle_connections(ipver, n, conns=4, cycle=(8, 8, 8, 8, 8, 8, 5), seed=0x7C0):
+    """n frames as `conns` connections of near-equal size (one list of frames each), every connection's payloads
+    cycling through `cycle`: with six 8s and a 5, every seventh frame is a short tail that ends a run."""
+    rng = np.random.default_rng(seed + ipver)
+    sizes = [n // conns + (i < n % conns) for i in range(conns)]
+    return [case_frames(flow_case(rng, ipver, np.resize(np.array(cycle), k))) for k in sizes if k]
+
+
 def frames_of(b, lead=0, rng=None):
     """The frames segmentation offload makes of batch b, packed densely behind `lead` bytes: (buf, offsets, valid
     bits)."""

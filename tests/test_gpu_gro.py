@@ -7,96 +7,35 @@ import numpy as np
 import pytest
 
 import _gro
+import _gro_gpu as G
 import _rx
 import _tso
 import _tx
-from _gpu import dev, host, setup_gpu, torch, nsx, mask_words
+from _gpu import host, setup_gpu, torch, nsx
 
 pytestmark = pytest.mark.gpu
 
-FILL = 0xAB
-_NP = {"uint8": np.uint8, "int16": np.uint16, "int32": np.uint32, "int64": np.uint64}
-_SIGNED = {np.dtype(np.uint8): np.uint8, np.dtype(np.uint16): np.int16, np.dtype(np.uint32): np.int32,
-           np.dtype(np.uint64): np.int64}
 F = _gro
+FILL = G.FILL
+_d, _fn, _filled, _want, _same, _check = G.d, G.fn, G.filled, G.want, G.same, G.check
 
 
 def setup_module(module):
     setup_gpu()
 
 
-def _d(a):
-    a = np.ascontiguousarray(a)
-    return dev(a.view(_SIGNED[a.dtype]))
-
-
-def _fn(ipver):
-    return nsx.gro_ipv4_tcp_dev if ipver == 4 else nsx.gro_ipv6_tcp_dev
-
-
-def _sizes(n, ipver, nbytes):
-    alen = 4 if ipver == 4 else 16
-    return {k: (dt, max(count(n, alen, nbytes), 1)) for k, dt, count in nsx.GRO_FIELDS}
-
-
-def _filled(n, ipver, nbytes):
-    """Every output at its worst-case size, each byte FILL."""
-    out = {}
-    for k, (dt, cnt) in _sizes(n, ipver, nbytes).items():
-        size = np.dtype(_NP[dt]).itemsize
-        out[k] = torch.full((cnt * size,), FILL, dtype=torch.uint8, device="cuda").view(getattr(torch, dt))
-    return out
-
-
 def _gpu(buf, offs, valid, ipver, tune=None, d_valid=None):
-    """One device call over FILL-filled outputs: dict of host arrays (unsigned views)."""
-    n = offs.size - 1
-    words = mask_words(F.valid_bits(valid, n).astype(np.uint8)) if d_valid is None else None
-    d_valid = _d(words if words.size else np.zeros(1, np.uint64)) if d_valid is None else d_valid
-    out = _filled(n, ipver, buf.size)
-    res = _fn(ipver)(_d(buf), _d(offs), d_valid, out=out, tune=tune)
-    assert all(res[k] is out[k] for k in out)
-    return {k: host(v).view(_NP[dt]) for (k, v), (dt, _) in zip(res.items(), _sizes(n, ipver, buf.size).values())}
-
-
-def _want(buf, offs, valid, ipver):
-    """The oracle's outputs laid into FILL-filled arrays of the worst-case sizes."""
-    n = offs.size - 1
-    o = F.gro(buf, offs, valid, ipver)
-    ns = o["n_super"]
-    want = {}
-    for k, (dt, cnt) in _sizes(n, ipver, buf.size).items():
-        size = np.dtype(_NP[dt]).itemsize
-        a = np.full(cnt * size, FILL, np.uint8).view(_NP[dt])
-        v = np.asarray([ns], np.uint64) if k == "n_super" else np.asarray(o[k]).reshape(-1)
-        a[:v.size] = v
-        want[k] = a
-    return want, o
-
-
-def _same(got, want, what=""):
-    for k in want:
-        if not np.array_equal(got[k], want[k]):
-            d = np.nonzero(got[k] != want[k])[0]
-            raise AssertionError(f"{what} {k}: {d.size} entries differ, first at {d[0]}: got {got[k][d[:8]]}, "
-                                 f"want {want[k][d[:8]]} (n_super got {got['n_super'][0]}, want {want['n_super'][0]})")
-
-
-def _check(buf, offs, valid, ipver, tunes=(None,), what=""):
-    want, o = _want(buf, offs, valid, ipver)
-    for tune in tunes:
-        _same(_gpu(buf, offs, valid, ipver, tune=tune), want, f"{what} tune={tune}")
-    return o
+    return G.gpu(buf, offs, valid, ipver, tune=tune, d_mask=d_valid)
 
 
 # ---------------------------------------------------------------- cut cases
 @pytest.mark.parametrize("opts", [False, True], ids=["noopt", "opts"])
-@pytest.mark.parametrize("mss", F.MSS_SET + (1,))
+@pytest.mark.parametrize("mss", F.MSS_SET + (1, 8960))
 @pytest.mark.parametrize("ipver", [4, 6])
 def test_gro_cut_cases(ipver, mss, opts):
     """The frames segmentation offload cuts at every cut length, behind 0-3 lead bytes (the source alignment): odd mss
     makes the payloads of neighbouring frames meet inside a dword at every byte position; mss 3 and 1 make payloads
-    shorter than a dword."""
+    shorter than a dword; mss 8960 (jumbo frames) makes every full payload five row pairs of the copy."""
     b = F.cut_batch(ipver, mss, opts, lead=1)
     for lead in range(4):
         buf, offs, valid = F.frames_of(b, lead=lead)
@@ -291,6 +230,100 @@ def test_gro_just_above_the_default_scan_block(ipver):
     assert offs.size - 1 == 4100
     o = _check(buf, offs, np.ones(4100, bool), ipver)
     assert o["n_super"] == 14 and o["frame_cnt"].tolist() == [300] * 13 + [200]
+
+
+# ---------------------------------------------------------------- the copy's row pairs
+ROW_PAIR_P = (2032, 2047, 2048, 2049, 2064, 4095, 4096, 4097, 8960)
+
+
+@functools.lru_cache(maxsize=None)
+def _row_pair_frames(ipver, opt, P, k):
+    """A one-frame connection with k payload bytes, then a second connection: three frames of P and a 5-byte tail."""
+    rng = np.random.default_rng(0x7B0 + 64 * P + 4 * k + ipver + opt)
+    ob = _tx.opt_bytes(rng, "mss") if opt else b""
+    return tuple(F.case_frames(F.flow_case(rng, ipver, [k], opt=ob)) +
+                 F.case_frames(F.flow_case(rng, ipver, [P, P, P, 5], opt=ob)))
+
+
+@pytest.mark.parametrize("P", ROW_PAIR_P)
+@pytest.mark.parametrize("opt", [False, True], ids=["noopt", "opt"])
+@pytest.mark.parametrize("ipver", [4, 6])
+def test_gro_row_pair_boundary(ipver, opt, P):
+    """The copy takes a payload in row pairs of 2 x 64 chunks of 16 bytes; a payload of more than 128 chunks goes
+    round the pair loop again (c0 > 0). The second super-segment's destination starts k bytes into a 16-byte chunk
+    (k = 0..15, the payload of the one-frame connection before it) and its source 0-3 lead bytes off, so the chunk
+    count ceil((k + P) / 16) crosses 128 (P around 2048), 256 (around 4096) and 560 (8960) at every destination and
+    source alignment; the frames after the first of the run start at k + P and k + 2P. Against the model, and through
+    segmentation offload on the device: every frame comes back."""
+    chunks = {(k + P + 15) // 16 for k in range(16)}
+    if P in (2047, 2048, 4095, 4096, 8960):
+        assert chunks == {(P + 15) // 16, (P + 15) // 16 + 1} and min(chunks) in (128, 256, 560)
+    for k in range(16):
+        frames = list(_row_pair_frames(ipver, opt, P, k))
+        for lead in range(4):
+            buf, offs = F.pack(frames, lead=lead)
+            valid = np.ones(5, bool)
+            o = _check(buf, offs, valid, ipver, what=f"k={k} lead={lead}")
+            assert o["frame_cnt"].tolist() == [1, 4] and o["data_off"].tolist() == [0, k, k + 3 * P + 5]
+            ps = G.assert_round_trip(buf, offs, valid, ipver, what=f"k={k} lead={lead}")
+            assert ps.tolist() == [0, 1, 2, 3, 4]
+
+
+# ---------------------------------------------------------------- maximal frames
+def _maximal_batch(ipver, opt):
+    """Three frames as long as the IP length field allows and a 9-byte tail (one connection), a frame with a valid
+    header and 200,000 bytes in all, for IPv6 a maximal frame with one byte appended (one more than its payload length
+    field can say), and a second connection of two small frames: (buf, offsets, the maximal payload)."""
+    rng = np.random.default_rng(0x7B8 + ipver + opt)
+    ob = _tx.opt_bytes(rng, "nop_nop_k2len10") if opt else b""
+    assert len(ob) == (12 if opt else 0)
+    top = _tx.WIRE_MAX[ipver] - 20 - len(ob)
+    frames = F.case_frames(F.flow_case(rng, ipver, [top, top, top, 9], opt=ob))
+    assert len(frames[0]) == (65535 if ipver == 4 else 65575)
+    long = frames[0] + rng.integers(0, 256, 200_000 - len(frames[0]), dtype=np.uint8).tobytes()
+    extra = [frames[2] + b"\x00"] if ipver == 6 else []
+    frames = frames + [long] + extra + F.case_frames(F.flow_case(rng, ipver, [100, 100]))
+    return F.pack(frames, lead=1 + opt) + (top,)
+
+
+@pytest.mark.parametrize("opt", [False, True], ids=["noopt", "opt12"])
+@pytest.mark.parametrize("ipver", [4, 6])
+def test_gro_maximal_frames(ipver, opt):
+    """IPv4 total length 65535 (payload 65495, 65483 behind 12 option bytes) and IPv6 payload length 65535 (a
+    65,575-byte frame): three of them and a tail are one super-segment whose mss is that payload, and segmentation
+    offload, its length limit exactly met, gives the frames back. A 200,000-byte frame and an IPv6 frame one byte
+    longer than its length field says are non-members although their valid bits are set."""
+    buf, offs, top = _maximal_batch(ipver, opt)
+    n = offs.size - 1
+    valid = np.ones(n, bool)
+    o = _check(buf, offs, valid, ipver, tunes=(None, dict(run_segs=16, blocks_per_cu=1)))
+    assert o["frame_cnt"].tolist() == [4, 2] and o["mss"].tolist() == [top, 100]
+    assert top == {(4, False): 65495, (4, True): 65483, (6, False): 65515, (6, True): 65503}[ipver, opt]
+    assert o["frame_seg"].tolist() == [0] * 4 + [F.NONE] * (n - 6) + [1, 1]
+    ps = G.assert_round_trip(buf, offs, valid, ipver)
+    assert ps.tolist() == [0, 1, 2, 3, n - 2, n - 1]
+    # keyed by flow: the same super-segments (in key order), the non-members last
+    g = _check(buf, offs, valid, ipver, flow=True)
+    assert sorted(g["frame_cnt"].tolist()) == [2, 4] and sorted(g["order"][:6].tolist()) == [0, 1, 2, 3, n - 2, n - 1]
+    assert sorted(G.assert_round_trip(buf, offs, valid, ipver, flow=True).tolist()) == [0, 1, 2, 3, n - 2, n - 1]
+
+
+# ---------------------------------------------------------------- the emit grid's second trip
+@pytest.mark.parametrize("ipver", [4, 6])
+def test_gro_emit_grid_takes_a_second_trip(ipver):
+    """The emit pass's grid is min(groups / 4, CUs x blocks_per_cu) workgroups of four 16-frame wave tasks: at
+    blocks_per_cu = 1, 64 x CUs + 21 frames send the first workgroups round the grid-stride loop again, the last of
+    them with a 5-frame group. Four connections delivered one after the other, every seventh frame a short tail that
+    ends a run, every 997th valid bit clear."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    n = 64 * cus + 21
+    assert n > 64 * cus and (n + 15) // 16 > 4 * cus
+    buf, offs = F.pack([f for c in F.cycle_connections(ipver, n) for f in c], lead=ipver % 4)
+    assert offs.size - 1 == n
+    valid = np.ones(n, bool)
+    valid[996::997] = False
+    o = _check(buf, offs, valid, ipver, tunes=(dict(blocks_per_cu=1),))
+    assert n // 7 <= o["n_super"] <= n // 7 + 4 + 2 * (n // 997 + 1) and o["frame_cnt"].max() == 7
 
 
 # ---------------------------------------------------------------- wraps

@@ -9,100 +9,45 @@ import pytest
 
 import _gro
 import _gro_flow as FL
+import _gro_gpu as G
 import _tx
-from _gpu import dev, host, setup_gpu, torch, nsx, mask_words
+from _gpu import host, setup_gpu, torch, nsx
 
 pytestmark = pytest.mark.gpu
 
-FILL = 0xAB
-_NP = {"uint8": np.uint8, "int16": np.uint16, "int32": np.uint32, "int64": np.uint64}
-_SIGNED = {np.dtype(np.uint8): np.uint8, np.dtype(np.uint16): np.int16, np.dtype(np.uint32): np.int32,
-           np.dtype(np.uint64): np.int64}
 F = _gro
+FILL = G.FILL
 MSS_OPT = b"\x02\x04\x05\xb4"
 SMALL_TILES = dict(rows=1, run_segs=16)  # 256 keys per sort tile, 16 frames per scan block
+_d, _d_valid, _same = G.d, G.d_valid, G.same
 
 
 def setup_module(module):
     setup_gpu()
 
 
-def _d(a):
-    a = np.ascontiguousarray(a)
-    return dev(a.view(_SIGNED[a.dtype]))
-
-
 def _fn(ipver, flow=True):
-    if flow:
-        return nsx.gro_flow_ipv4_tcp_dev if ipver == 4 else nsx.gro_flow_ipv6_tcp_dev
-    return nsx.gro_ipv4_tcp_dev if ipver == 4 else nsx.gro_ipv6_tcp_dev
-
-
-def _sizes(n, ipver, nbytes, flow=True):
-    alen = 4 if ipver == 4 else 16
-    s = {k: (dt, max(count(n, alen, nbytes), 1)) for k, dt, count in nsx.GRO_FIELDS}
-    if flow:
-        s["order"] = ("int32", max(n, 1))
-    return s
+    return G.fn(ipver, flow)
 
 
 def _filled(n, ipver, nbytes, flow=True):
-    """Every output (and the order) at its worst-case size, each byte FILL."""
-    out = {}
-    for k, (dt, cnt) in _sizes(n, ipver, nbytes, flow).items():
-        size = np.dtype(_NP[dt]).itemsize
-        out[k] = torch.full((cnt * size,), FILL, dtype=torch.uint8, device="cuda").view(getattr(torch, dt))
-    return out
+    return G.filled(n, ipver, nbytes, flow)
 
 
 def _host(res, n, ipver, nbytes, flow=True):
-    return {k: host(res[k]).view(_NP[dt]) for k, (dt, _) in _sizes(n, ipver, nbytes, flow).items()}
-
-
-def _d_valid(valid, n):
-    words = mask_words(F.valid_bits(valid, n).astype(np.uint8))
-    return _d(words if words.size else np.zeros(1, np.uint64))
+    return G.to_host(res, n, ipver, nbytes, flow)
 
 
 def _gpu(buf, offs, valid, ipver, tune=None, d_valid=None, flow=True):
-    """One device call over FILL-filled outputs: dict of host arrays (unsigned views)."""
-    n = offs.size - 1
-    d_valid = _d_valid(valid, n) if d_valid is None else d_valid
-    out = _filled(n, ipver, buf.size, flow)
-    order = out.pop("order", None)
-    kw = dict(order=order) if flow else {}
-    res = _fn(ipver, flow)(_d(buf), _d(offs), d_valid, out=out, tune=tune, **kw)
-    assert all(res[k] is out[k] for k in out) and (not flow or res["order"] is order)
-    return _host(res, n, ipver, buf.size, flow)
+    return G.gpu(buf, offs, valid, ipver, tune=tune, d_mask=d_valid, flow=flow)
 
 
 def _want(buf, offs, valid, ipver, flow=True):
-    """The model's outputs laid into FILL-filled arrays of the worst-case sizes."""
-    n = offs.size - 1
-    o = (FL.gro_flow if flow else F.gro)(buf, offs, valid, ipver)
-    want = {}
-    for k, (dt, cnt) in _sizes(n, ipver, buf.size, flow).items():
-        size = np.dtype(_NP[dt]).itemsize
-        a = np.full(cnt * size, FILL, np.uint8).view(_NP[dt])
-        v = np.asarray([o["n_super"]], np.uint64) if k == "n_super" else np.asarray(o[k]).reshape(-1)
-        a[:v.size] = v
-        want[k] = a
-    return want, o
-
-
-def _same(got, want, what=""):
-    for k in ["order"] * ("order" in want) + [k for k in want if k != "order"]:
-        if not np.array_equal(got[k], want[k]):
-            d = np.nonzero(got[k] != want[k])[0]
-            raise AssertionError(f"{what} {k}: {d.size} entries differ, first at {d[0]}: got {got[k][d[:8]]}, "
-                                 f"want {want[k][d[:8]]} (n_super got {got['n_super'][0]}, want {want['n_super'][0]})")
+    return G.want(buf, offs, valid, ipver, flow)
 
 
 def _check(buf, offs, valid, ipver, tunes=(None,), what=""):
-    want, o = _want(buf, offs, valid, ipver)
-    for tune in tunes:
-        _same(_gpu(buf, offs, valid, ipver, tune=tune), want, f"{what} tune={tune}")
-    return o
+    return G.check(buf, offs, valid, ipver, tunes=tunes, what=what, flow=True)
 
 
 # ---------------------------------------------------------------- interleave
@@ -163,6 +108,109 @@ def test_flow_table_scan_takes_more_than_one_sweep(ipver):
     valid[::97] = False
     _check(buf, offs, valid, ipver, tunes=(SMALL_TILES, dict(rows=64), dict(rows=1000)))
     assert np.unique(FL.keys(buf, offs, valid, ipver)).size == 62
+
+
+# ---------------------------------------------------------------- the sort's key distributions
+def _keyed(frames, ipver, key):
+    """The frames moved to the connection whose flow key is `key` (ports crafted, checksums re-fixed)."""
+    return [FL.with_ports(f, ipver, FL.ports_for_key(FL.state(f, ipver), key)) for f in frames]
+
+
+def _interleave(rng, conns):
+    """A random interleave of the connections' frames, each connection's own frames in order."""
+    who = rng.permutation(np.repeat(np.arange(len(conns)), [len(c) for c in conns]))
+    nxt = [0] * len(conns)
+    frames = []
+    for w in who:
+        frames.append(conns[w][nxt[w]])
+        nxt[w] += 1
+    return frames
+
+
+@functools.lru_cache(maxsize=None)
+def _key_distribution(ipver, dist):
+    """(frames, valid, the keys the frames were made for - None where the frame is no member)."""
+    rng = np.random.default_rng(0x610 + ipver)
+    if dist == "one_connection":  # 700 frames of one key: every wave step of every pass has 64 equal digits
+        frames = F.case_frames(F.flow_case(rng, ipver, [4] * 700))
+        return tuple(frames), np.ones(700, bool), None
+    if dist == "descending":  # 700 one-frame connections, keys strictly falling: the order is the exact reverse
+        keys = np.sort(rng.choice(0xFFFFFFFF, 700, replace=False))[::-1]
+        base = F.case_frames(F.flow_case(rng, ipver, [4] * 700))
+        frames = [_keyed([f], ipver, int(k))[0] for f, k in zip(base, keys)]
+        return tuple(frames), np.ones(700, bool), keys
+    if dist.startswith("byte"):  # all 256 values in one key byte, the other three constant; every key three times
+        shift = 8 * int(dist[4])
+        const = int(rng.integers(1 << 32)) & ~(0xFF << shift) & 0xFFFFFFFF
+        if shift == 24:
+            const &= ~1  # 0xFFFFFFFF stays the non-members' key alone
+        conns = FL.connections(rng, ipver, [(4, 4, 4)] * 256)
+        conns = [_keyed(c, ipver, const | (int(j) << shift)) for j, c in zip(rng.permutation(256), conns)]
+        return tuple(_interleave(rng, conns)), np.ones(768, bool), None
+    assert dist == "extremes"  # keys 0 and 0xFFFFFFFE alternate, every fifth frame a non-member (0xFFFFFFFF)
+    a, b = FL.connections(rng, ipver, [[4] * 300, [4] * 300])
+    a, b = _keyed(a, ipver, 0), _keyed(b, ipver, 0xFFFFFFFE)
+    frames, valid = [], []
+    for i in range(300):
+        frames += [a[i], b[i]]
+        valid += [True, True]
+        if i % 2 == 0:  # a truncated frame, or a whole one whose valid bit is clear
+            frames.append(a[i][:30] if i % 4 == 0 else b[i])
+            valid.append(i % 4 == 0)
+    return tuple(frames), np.array(valid), None
+
+
+KEY_DISTS = ("one_connection", "descending", "byte0", "byte1", "byte2", "byte3", "extremes")
+
+
+@pytest.mark.parametrize("dist", KEY_DISTS)
+@pytest.mark.parametrize("ipver", [4, 6])
+def test_flow_sort_key_distributions(ipver, dist):
+    """Keys crafted through the ports, 700-768 frames (three tiles at rows = 1, one by default). One connection: 64
+    equal digits in every wave step, the order the identity across waves and tiles. Strictly descending keys: the
+    exact reverse. All 256 values in one key byte and the others constant: that pass permutes with every digit in use
+    (64 different digits in a wave step) while the other three must keep the order. Keys 0 and 0xFFFFFFFE alternating
+    among non-members: the extreme digits in every pass. The order against a stable argsort of the keys, and every
+    output against the model."""
+    frames, valid, made = _key_distribution(ipver, dist)
+    n = len(frames)
+    assert 600 <= n <= 1100
+    buf, offs = F.pack(list(frames), lead=n % 4)
+    o = _check(buf, offs, valid, ipver, tunes=(dict(rows=1), None), what=dist)
+    keys = FL.keys(buf, offs, valid, ipver)
+    assert np.array_equal(o["order"], np.argsort(keys, kind="stable"))
+    if dist == "one_connection":
+        assert np.unique(keys).size == 1 and o["order"].tolist() == list(range(n)) and o["frame_cnt"].tolist() == [n]
+    elif dist == "descending":
+        assert np.array_equal(keys, made) and (np.diff(keys.astype(np.int64)) < 0).all()
+        assert o["order"].tolist() == list(range(n))[::-1] and o["n_super"] == n
+    elif dist.startswith("byte"):
+        shift = 8 * int(dist[4])
+        assert np.unique(keys).size == 256 and np.unique(keys >> shift & 0xFF).size == 256
+        assert np.unique(keys & ~np.uint32(0xFF << shift)).size == 1
+        assert o["n_super"] == 256 and (o["frame_cnt"] == 3).all()
+    else:
+        assert set(keys.tolist()) == {0, 0xFFFFFFFE, 0xFFFFFFFF} and o["frame_cnt"].tolist() == [300, 300]
+        assert o["order"][:300].tolist() == [i for i in range(n) if keys[i] == 0]
+
+
+# ---------------------------------------------------------------- the emit grid's second trip
+@pytest.mark.parametrize("ipver", [4, 6])
+def test_flow_emit_grid_takes_a_second_trip(ipver):
+    """The batch of test_gpu_gro.py's test of that name (64 x CUs + 21 frames, four connections whose every seventh
+    frame ends a run, every 997th valid bit clear) delivered round-robin, at blocks_per_cu = 1: the ordered emit
+    pass goes round its grid-stride loop again, once behind one sort tile per 4,096 keys and once behind one per 256."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    n = 64 * cus + 21
+    assert n > 64 * cus and (n + 15) // 16 > 4 * cus
+    frames, _ = FL.round_robin(F.cycle_connections(ipver, n))
+    buf, offs = F.pack(frames, lead=ipver % 4)
+    assert offs.size - 1 == n
+    valid = np.ones(n, bool)
+    valid[996::997] = False
+    o = _check(buf, offs, valid, ipver, tunes=(dict(blocks_per_cu=1), dict(blocks_per_cu=1, rows=1)))
+    assert n // 7 <= o["n_super"] <= n // 7 + 4 + 2 * (n // 997 + 1) and o["frame_cnt"].max() == 7
+    assert np.unique(FL.keys(buf, offs, valid, ipver)).size == 5
 
 
 # ---------------------------------------------------------------- collisions
