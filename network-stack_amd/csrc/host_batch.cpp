@@ -10,6 +10,8 @@
 // before the first copy — validation, shard bounds, chunk cuts, staging layout — is host_plan.h's. Caller memory
 // that is already pinned (nsx_alloc_pinned) is DMA'd directly; pageable memory is bounced through pinned staging
 // buffers (multi-threaded copy, stage_copy). Streams and buffers persist per device (DevCtx).
+// NSX_HOST_EXACT_BUFFERS (never defined by the product build) makes every staging buffer exactly as large as was
+// reserved, for tests/test_host_batch_cpp.py, which runs this file on a CPU model of HIP under sanitizers.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -90,8 +92,12 @@ struct Grow {
     hipError_t ensure(uint64_t bytes) {
         if (bytes <= cap) return hipSuccess;
         release();
+#ifdef NSX_HOST_EXACT_BUFFERS
+        const uint64_t c = bytes;  // the sanitizer builds: a buffer reserved a byte short is a report
+#else
         uint64_t c = 4096;
         while (c < bytes) c <<= 1;
+#endif
         const hipError_t e = kHost ? hipHostMalloc(&p, c, hipHostMallocPortable) : hipMalloc(&p, c);
         if (e != hipSuccess) {
             p = nullptr;
