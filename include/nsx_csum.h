@@ -546,6 +546,101 @@ nsx_gro_flow_ipv6_tcp_dev(const void* d_base, const uint64_t* d_offsets, uint64_
                           uint32_t* d_order, const nsx_gro_out* out, void* d_work, uint64_t work_bytes,
                           nsx_stream_t stream);
 
+/* In-place NAT rewrite with incremental checksum update (RFC 1071 §2(4),
+ * RFC 1624): the frames of a receive batch, that pass's validity mask and a
+ * translation table in; the same frames out, the matching ones with new
+ * addresses, ports and TTL / hop limit and both checksums corrected from the
+ * old and new field values alone — the payload is neither read nor written. A
+ * bitmask says which frames were translated. Input as the receive pass: d_base
+ * (written here), d_offsets (n + 1), n, and d_valid, that pass's bitmask over
+ * the same frames (required).
+ *
+ * Tuple. The bytes as they stand on the wire. IPv4: 12 bytes — IP header bytes
+ * 12-19 (src, dst), then TCP bytes 0-3 (the two ports; the TCP header starts
+ * IHL*4 bytes into the frame). IPv6: 36 bytes — IP header bytes 8-39, then TCP
+ * bytes 0-3 (frame bytes 40-43). h_match and h_new are n_rules tuples each,
+ * packed: rule r turns the tuple h_match[r] into the tuple h_new[r].
+ *
+ * Table. slots entries, slots a power of two; an entry is two tuples with a
+ * state dword between them:
+ *                                IPv4 (32 B per entry)   IPv6 (80 B per entry)
+ *   match tuple                  bytes 0-11              bytes 0-35
+ *   state (little-endian dword)  bytes 12-15             bytes 36-39
+ *   new tuple                    bytes 16-27             bytes 40-75
+ *   zero                         bytes 28-31             bytes 76-79
+ * State 1 means occupied; any other state value means empty. The table base
+ * must be 16-byte aligned (NSX_EINVAL otherwise).
+ *
+ * Hash. h = 0x811C9DC5; for each little-endian dword w of the tuple, in order
+ * (3 dwords for IPv4, 9 for IPv6), h = ((h ^ w) * 0x01000193) mod 2^32; the home
+ * slot is h & (slots - 1). This is the same key that nsx_gro_flow_* defines for
+ * a member: FNV-1a over the address dwords, then the ports.
+ *
+ * Lookup. Probe home, home + 1, ... modulo slots. The first entry that is not
+ * occupied ends the lookup with a miss; an occupied entry whose match tuple
+ * equals the frame's tuple, all of its bytes, is a hit (the hash alone is never
+ * a match); after slots probes the lookup is a miss. This is a total function
+ * of arbitrary table bytes: a table without an empty entry costs slots probes
+ * per frame and nothing else.
+ *
+ * nsx_nat_table_slots gives the smallest power of two >= max(16, 2*n_rules)
+ * (NSX_EINVAL: a NULL out_slots, n_rules >= 2^31). nsx_nat_table_build_host
+ * zero-fills the slots entries at h_table and inserts the rules in order, each
+ * into the first entry its lookup finds not occupied. NSX_EINVAL: ip_ver not 4
+ * or 6; a NULL h_match or h_new with n_rules > 0, a NULL h_table; slots not a
+ * power of two, slots < 2*n_rules, slots < 16 or slots > 2^31; two rules with
+ * the same match tuple (the table's contents are then unspecified). Host
+ * memory only, no GPU needed; the caller copies the table to the device.
+ *
+ * Rewrite. Frame i is translated iff its d_valid bit is set; it is well-formed
+ * as the receive pass of its IP version defines (the length, version, protocol
+ * and fragment conditions above — re-checked here, so a wrong mask never makes
+ * the kernel touch a byte outside the frame's own range, nor a frame whose bit
+ * is clear at all); its TTL (IPv4 byte 8) / hop limit (IPv6 byte 7) t satisfies
+ * t > ttl_dec; and its tuple hits the table. ttl_dec > 255 is NSX_EINVAL,
+ * ttl_dec = 0 is allowed. The TCP data offset is not looked at. IPv4 frames
+ * with IP options (IHL > 5) are translated like any other. A frame that is not
+ * translated is left byte for byte as it was. Bit (i % 64) of d_hit[i / 64] is
+ * set iff frame i was translated; bits past n are 0; d_hit has ceil(n/64) words
+ * and is required. No byte outside a translated frame's own range is written,
+ * whatever the alignment of the frames.
+ *
+ * A translated frame changes only in: TTL / hop limit, which becomes
+ * t - ttl_dec; src and dst, the address part of the new tuple; TCP bytes 0-3,
+ * the port part of the new tuple; IPv4 header bytes 10-11 (the header
+ * checksum); TCP bytes 16-17 (the TCP checksum).
+ *
+ * Checksum update (RFC 1624 eqn. 3), evaluated exactly so. Let fold(x) = 0 if
+ * x = 0, else 1 + (x - 1) mod 0xFFFF. For a checksum field HC (read big-endian)
+ * and the big-endian 16-bit words m_k -> m'_k it covers, every listed word
+ * included whether or not its value changed:
+ *   HC' = ~fold((~HC & 0xFFFF) + SUM_k ((~m_k & 0xFFFF) + m'_k)) & 0xFFFF.
+ * The IPv4 header checksum covers the word at bytes 8-9 (TTL, protocol) and
+ * the 4 address words; the IPv4 TCP checksum the 4 address words (its
+ * pseudo-header) and the 2 port words; the IPv6 TCP checksum the 16 address
+ * words and the 2 port words. The hop limit is covered by no checksum.
+ * Consequence: for a frame whose checksum verified before, the new field equals
+ * what a full recomputation over the rewritten frame stores (~sum with the
+ * field zero, as the transmit pass writes it), bit for bit; for a frame whose
+ * checksum was wrong, it stays wrong by the same one's-complement difference.
+ *
+ * NSX_EINVAL before anything else: a NULL pointer (d_base, d_valid and d_hit may
+ * be NULL when n == 0), n >= 2^32 - 1, slots not a power of two or > 2^31, a
+ * misaligned table, ttl_dec > 255. Then NSX_ENODEV without a GPU. No
+ * allocation, no host sync, no per-stream counters: one launch (none for
+ * n == 0), which can be captured into a graph. There are no _host forms (header
+ * edits over PCIe make no sense), no _tuned twins (one lane per frame: there is
+ * no launch shape to override) and no multi-GPU sharding. */
+int nsx_nat_table_slots(uint64_t n_rules, uint64_t* out_slots);
+int nsx_nat_table_build_host(uint32_t ip_ver, const uint8_t* h_match, const uint8_t* h_new, uint64_t n_rules,
+                             void* h_table, uint64_t slots);
+int nsx_nat_ipv4_tcp_rewrite_dev(void* d_base, const uint64_t* d_offsets, uint64_t n, const uint64_t* d_valid,
+                                 const void* d_table, uint64_t slots, uint32_t ttl_dec, uint64_t* d_hit,
+                                 nsx_stream_t stream);
+int nsx_nat_ipv6_tcp_rewrite_dev(void* d_base, const uint64_t* d_offsets, uint64_t n, const uint64_t* d_valid,
+                                 const void* d_table, uint64_t slots, uint32_t ttl_dec, uint64_t* d_hit,
+                                 nsx_stream_t stream);
+
 /* ----------------------------------------------------------------------------
  * Host-resident batches: pinned staging, H2D → kernel → D2H double-buffered
  * over two streams per GPU, segments sharded contiguously across num_gpus

@@ -1,5 +1,5 @@
-// api_util.h — what csum_api.cpp and host_batch.cpp share: the ABI structs as the launchers' structs, the HIP
-// error mapping and the cached per-device CU count (both defined in csum_api.cpp).
+// api_util.h — what csum_api.cpp, host_batch.cpp and nat_api.cpp share: the ABI structs as the launchers' structs,
+// the HIP error mapping, the calling thread's device and the cached per-device CU count (all defined in csum_api.cpp).
 #pragma once
 #include "../../include/nsx_csum.h"
 #include "csum_kernels.h"
@@ -9,6 +9,7 @@ namespace nsx {
 int map_err(hipError_t e);  // NSX_OK / NSX_ENOMEM / NSX_ENODEV / NSX_EIO; clears HIP's last error
 int device_cus(int dev);    // compute units of device `dev`, queried once; 0 when it cannot be used
 int device_count();         // 0 when HIP reports none or fails
+int current_device();       // current device of the calling thread, or -1 when there is no usable GPU
 
 inline TcpHdrSoA to_soa(const nsx_tcp_hdr_soa& h) {
     return {h.src_port, h.dst_port, h.seq_num, h.ack_num, h.offset, h.control, h.window, h.urgent_ptr};

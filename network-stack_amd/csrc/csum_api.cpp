@@ -23,17 +23,7 @@ constexpr int kMaxDevices = 64;
 int g_cus[kMaxDevices];  // compute units per device, 0 = unusable; queried once
 std::once_flag g_dev_once[kMaxDevices];
 
-// Current device of the calling thread, or -1 when there is no usable GPU.
-int current_device() {
-    if (nsx::device_count() <= 0) return -1;
-    int d = -1;
-    if (hipGetDevice(&d) != hipSuccess) {
-        (void)hipGetLastError();
-        return -1;
-    }
-    return nsx::device_cus(d) > 0 ? d : -1;
-}
-
+using nsx::current_device;
 using nsx::map_err;
 using nsx::to_soa;
 
@@ -63,6 +53,16 @@ int device_cus(int dev) {
             (void)hipGetLastError();
     });
     return g_cus[dev];
+}
+
+int current_device() {
+    if (device_count() <= 0) return -1;
+    int d = -1;
+    if (hipGetDevice(&d) != hipSuccess) {
+        (void)hipGetLastError();
+        return -1;
+    }
+    return device_cus(d) > 0 ? d : -1;
 }
 
 int map_err(hipError_t e) {

@@ -1,6 +1,6 @@
-// csum_kernels.h — internal launcher interface between the C ABI (csum_api.cpp,
-// host_batch.cpp) and the gfx950 kernels (csum_kernels.hip, gro_kernels.hip, gro_flow_kernels.hip). Not a public
-// header.
+// csum_kernels.h — internal launcher interface between the C ABI (csum_api.cpp, nat_api.cpp,
+// host_batch.cpp) and the gfx950 kernels (csum_kernels.hip, gro_kernels.hip, gro_flow_kernels.hip,
+// nat_kernels.hip). Not a public header.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -133,6 +133,10 @@ uint64_t gro_flow_work_bytes(uint64_t n);
 // 1..64).
 hipError_t launch_gro_flow(const LaunchCfg& c, int ipver, const void* d_base, const uint64_t* d_offsets, uint64_t n,
                            const uint64_t* valid, uint32_t* d_order, const GroOut& o, void* work, hipStream_t st);
+// The in-place NAT rewrite (nsx_nat_*, nat_kernels.hip): one launch, a lane per frame; none for n == 0. n < 2^32 - 1,
+// slots a power of two <= 2^31, the table 16-byte aligned, ttl_dec <= 255 (nat_api.cpp checks all of it).
+hipError_t launch_nat_rewrite(int ipver, void* d_base, const uint64_t* d_offsets, uint64_t n, const uint64_t* valid,
+                              const void* d_table, uint64_t slots, uint32_t ttl_dec, uint64_t* d_hit, hipStream_t st);
 struct TcpParsedSoA {  // device arrays, one entry per segment; every member nullable
     uint16_t* src_port;
     uint16_t* dst_port;

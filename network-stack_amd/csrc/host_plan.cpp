@@ -3,6 +3,7 @@
 #include "host_plan.h"
 
 #include <algorithm>
+#include <cstring>
 
 #include "host_csum.h"
 
@@ -195,6 +196,43 @@ bool tso_layout_ok(uint32_t iph, const uint64_t* opt_off, const uint64_t* data_o
     });
 }
 
+// ---- the NAT rewrite's translation table ----
+uint32_t nat_hash(const uint8_t* t, uint32_t tuple_bytes) {
+    uint32_t h = 0x811C9DC5u;
+    for (uint32_t k = 0; k < tuple_bytes; k += 4) {
+        const uint32_t lo = (uint32_t)t[k] | (uint32_t)t[k + 1] << 8, hi = (uint32_t)t[k + 2] | (uint32_t)t[k + 3] << 8;
+        h = (h ^ (lo | hi << 16)) * 0x01000193u;
+    }
+    return h;
+}
+
+bool nat_table_build(uint32_t ip_ver, const uint8_t* match, const uint8_t* repl, uint64_t n_rules, uint8_t* table,
+                     uint64_t slots) {
+    if ((ip_ver != 4 && ip_ver != 6) || !table || (n_rules && (!match || !repl))) return false;
+    if (!nat_slots_ok(slots) || slots < 16 || n_rules > slots / 2) return false;
+    const uint32_t tb = nat_tuple_bytes(ip_ver), eb = nat_entry_bytes(ip_ver);
+    std::memset(table, 0, slots * eb);
+    for (uint64_t r = 0; r < n_rules; ++r) {
+        const uint8_t* m = match + r * tb;
+        const uint64_t home = nat_hash(m, tb) & (slots - 1);
+        bool placed = false;
+        for (uint64_t p = 0; p < slots && !placed; ++p) {  // at most half the entries are occupied: an empty one exists
+            uint8_t* e = table + ((home + p) & (slots - 1)) * eb;
+            const bool occupied = e[tb] == 1 && !e[tb + 1] && !e[tb + 2] && !e[tb + 3];
+            if (occupied) {
+                if (!std::memcmp(e, m, tb)) return false;  // a second rule for one match tuple
+                continue;
+            }
+            std::memcpy(e, m, tb);
+            e[tb] = 1;  // the state dword, little-endian
+            std::memcpy(e + tb + 4, repl + r * tb, tb);
+            placed = true;
+        }
+        if (!placed) return false;
+    }
+    return true;
+}
+
 }  // namespace nsx
 
 extern "C" {
@@ -239,6 +277,20 @@ int nsx_tso_layout_host(const uint64_t* h_opt_off, const uint64_t* h_data_off, c
     });
     h_out_off[frames] = at;
     return NSX_OK;
+}
+
+int nsx_nat_table_slots(uint64_t n_rules, uint64_t* out_slots) {
+    if (!out_slots || n_rules >= (1ull << 31)) return NSX_EINVAL;
+    uint64_t s = 16;
+    while (s < 2 * n_rules) s <<= 1;
+    *out_slots = s;
+    return NSX_OK;
+}
+
+int nsx_nat_table_build_host(uint32_t ip_ver, const uint8_t* h_match, const uint8_t* h_new, uint64_t n_rules,
+                             void* h_table, uint64_t slots) {
+    return nsx::nat_table_build(ip_ver, h_match, h_new, n_rules, static_cast<uint8_t*>(h_table), slots) ? NSX_OK
+                                                                                                      : NSX_EINVAL;
 }
 
 }  // extern "C"

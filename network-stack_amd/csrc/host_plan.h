@@ -82,4 +82,18 @@ bool tso_layout_ok(uint32_t ip_hdr_len, const uint64_t* opt_off, const uint64_t*
                    uint64_t n, const uint32_t* frame_seg, const uint64_t* out_off, uint64_t n_frames,
                    uint64_t* seg_out, bool* gaps);
 
+// ---- the NAT rewrite's translation table (include/nsx_csum.h nsx_nat_*) ----
+// Tuple and entry bytes per IP version: 12 / 32 (IPv4), 36 / 80 (IPv6). An entry: match tuple, state dword
+// (little-endian, 1 = occupied), new tuple, zero dword.
+constexpr uint64_t kNatMaxSlots = 1ull << 31;
+inline uint32_t nat_tuple_bytes(uint32_t ip_ver) { return ip_ver == 6 ? 36u : 12u; }
+inline uint32_t nat_entry_bytes(uint32_t ip_ver) { return 2u * nat_tuple_bytes(ip_ver) + 8u; }
+inline bool nat_slots_ok(uint64_t slots) { return slots && !(slots & (slots - 1)) && slots <= kNatMaxSlots; }
+// FNV-1a over the tuple's little-endian dwords: nsx_gro_flow_*'s flow key.
+uint32_t nat_hash(const uint8_t* tuple, uint32_t tuple_bytes);
+// Zero-fills the table and inserts the rules in order by linear probing from the home slot. False (arguments the
+// header refuses, or two rules with one match tuple) is NSX_EINVAL.
+bool nat_table_build(uint32_t ip_ver, const uint8_t* match, const uint8_t* repl, uint64_t n_rules, uint8_t* table,
+                     uint64_t slots);
+
 }  // namespace nsx

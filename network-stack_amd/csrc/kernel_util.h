@@ -1,5 +1,5 @@
 // kernel_util.h — device helpers shared by the kernel files (csum_kernels.hip, gro_kernels.hip,
-// gro_flow_kernels.hip): the wave / row constants, the 16-byte chunk type, buffer descriptors and their 16-byte
+// gro_flow_kernels.hip, nat_kernels.hip): the wave / row constants, the 16-byte chunk type, buffer descriptors and their 16-byte
 // loads, byte masks, the v_alignbyte realignment, and receive coalescing's clamped frame window (FrameWin) and
 // membership test. Everything is __forceinline__ in an unnamed namespace, so each kernel file gets its own copies and
 // the code generated for a kernel does not depend on which file defines the helper

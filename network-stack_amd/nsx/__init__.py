@@ -137,13 +137,17 @@ def lib() -> ctypes.CDLL:
             "nsx_gro_flow_ipv6_tcp_dev": [vp, vp, u64, vp, vp, vp, vp, u64, vp],
             "nsx_gro_flow_ipv4_tcp_dev_tuned": [vp, vp, u64, vp, vp, vp, vp, u64, vp, vp],
             "nsx_gro_flow_ipv6_tcp_dev_tuned": [vp, vp, u64, vp, vp, vp, vp, u64, vp, vp],
+            "nsx_nat_table_slots": [u64, ctypes.POINTER(u64)],
+            "nsx_nat_table_build_host": [u32, vp, vp, u64, vp, u64],
+            "nsx_nat_ipv4_tcp_rewrite_dev": [vp, vp, u64, vp, vp, u64, u32, vp, vp],
+            "nsx_nat_ipv6_tcp_rewrite_dev": [vp, vp, u64, vp, vp, u64, u32, vp, vp],
             "nsx_fixed_launch_count": [u64, u32, u64, vp, ctypes.POINTER(u64)],
             "nsx_ipv4_hdr_launch_count": [vp, u64, u32, u64, vp, ctypes.POINTER(u64)],
         }
         # present since ABI round 6, and the transmit pass since its own change; an older library (same-box A/B against a
         # previous build) lacks them
         optional = {"nsx_stream_release", "nsx_deal_sets_in_use"} | \
-            {k for k in sig if k.startswith(("nsx_tx_", "nsx_tso_", "nsx_gro_"))}
+            {k for k in sig if k.startswith(("nsx_tx_", "nsx_tso_", "nsx_gro_", "nsx_nat_"))}
         for name, args in sig.items():
             if name in optional and not hasattr(L, name):
                 continue
@@ -1062,6 +1066,81 @@ def gro_flow_ipv4_tcp_dev(buf, offsets, valid, out=None, order=None, work=None, 
 def gro_flow_ipv6_tcp_dev(buf, offsets, valid, out=None, order=None, work=None, stream=None, tune=None) -> dict:
     """The same for IPv6."""
     return _gro_dev(6, buf, offsets, valid, out, work, stream, tune, flow=True, order=order)
+
+
+# ---------------------------------------------------------------------------
+# in-place NAT rewrite with incremental checksum update (nsx_nat_*)
+# ---------------------------------------------------------------------------
+NAT_TUPLE_BYTES = {4: 12, 6: 36}  # src, dst, the two ports, as on the wire
+NAT_ENTRY_BYTES = {4: 32, 6: 80}  # match tuple, state dword, new tuple, zero dword
+
+
+def nat_table_slots(n_rules: int) -> int:
+    """nsx_nat_table_slots: the smallest power of two >= max(16, 2 * n_rules)."""
+    c = ctypes.c_uint64(0)
+    _check(lib().nsx_nat_table_slots(n_rules, ctypes.byref(c)), "nsx_nat_table_slots")
+    return c.value
+
+
+def nat_table_build_host(ip_ver: int, match: np.ndarray, new: np.ndarray, slots: int | None = None) -> np.ndarray:
+    """nsx_nat_table_build_host: `match` and `new` are (n_rules, 12) (IPv4) or (n_rules, 36) (IPv6) uint8 tuples;
+    returns the table, slots * 32 or slots * 80 bytes of host memory (slots defaults to nat_table_slots(n_rules)),
+    for the caller to copy to the device."""
+    if ip_ver not in NAT_TUPLE_BYTES:
+        raise ValueError(f"nat_table_build_host: ip_ver must be 4 or 6, got {ip_ver}")
+    tb = NAT_TUPLE_BYTES[ip_ver]
+    match, new = np.ascontiguousarray(match, np.uint8), np.ascontiguousarray(new, np.uint8)
+    if match.size % tb or match.size != new.size:
+        raise ValueError(f"nat_table_build_host: match and new must hold the same number of {tb}-byte tuples, got "
+                         f"{match.size} B and {new.size} B")
+    n_rules = match.size // tb
+    if slots is None:
+        slots = nat_table_slots(n_rules)
+    if not 0 <= slots <= 1 << 31:  # refused by the C call too; checked here before the table is allocated
+        raise NsxError(NSX_EINVAL, "nsx_nat_table_build_host")
+    table = np.empty(max(slots * NAT_ENTRY_BYTES[ip_ver], 1), np.uint8)
+    _check(lib().nsx_nat_table_build_host(ip_ver, _np_ptr(match), _np_ptr(new), n_rules, _np_ptr(table), slots),
+           "nsx_nat_table_build_host")
+    return table[:slots * NAT_ENTRY_BYTES[ip_ver]]
+
+
+def _nat_rewrite_dev(ipver: int, buf, offsets, valid, table, slots: int, ttl_dec: int, hit, stream):
+    import torch
+    what = f"nat_ipv{ipver}_tcp_rewrite_dev"
+    n = _count(offsets, f"{what} offsets")
+    words = (n + 63) // 64
+    _span(buf, 0, f"{what} buf", elem=1)
+    if valid is None:
+        raise ValueError(f"{what}: the receive pass's mask `valid` is required")
+    _span(valid, 8 * words, f"{what} valid", elem=8)
+    if table is None:
+        raise ValueError(f"{what}: `table` is required")
+    if slots < 0 or slots > 1 << 31:
+        raise ValueError(f"{what}: slots must be a power of two <= 2^31, got {slots}")
+    _span(table, slots * NAT_ENTRY_BYTES[ipver], f"{what} table")
+    if hit is None:  # never a zero-size tensor, whose address is NULL
+        hit = torch.empty(max(words, 1), dtype=torch.int64, device=offsets.device)  # u64 bits
+    _span(hit, 8 * words, f"{what} hit", elem=8)
+    if not 0 <= ttl_dec < 1 << 32:  # what a uint32_t can carry; the C call refuses 256 and up (NSX_EINVAL)
+        raise ValueError(f"{what}: ttl_dec must be 0..255, got {ttl_dec}")
+    fn = getattr(lib(), f"nsx_{what}")
+    _check(fn(_dev_ptr(buf), _dev_ptr(offsets), n, _dev_ptr(valid), _dev_ptr(table), slots, ttl_dec, _dev_ptr(hit),
+              _stream(stream)), f"nsx_{what}")
+    return hit
+
+
+def nat_ipv4_tcp_rewrite_dev(buf, offsets, valid, table, slots: int, ttl_dec: int = 0, hit=None, stream=None):
+    """In-place NAT rewrite over packed IPv4/TCP frames (nsx_nat_ipv4_tcp_rewrite_dev): buf / offsets as
+    rx_ipv4_tcp_verify_dev, valid = that pass's mask, table = nat_table_build_host's bytes on the device (slots
+    entries). Frames whose address / port tuple hits the table get the new tuple, TTL - ttl_dec and incrementally
+    updated checksums, in `buf` itself. Returns `hit`: bit i%64 of hit[i//64] iff frame i was translated (int64
+    words, allocated unless given). Does not synchronise."""
+    return _nat_rewrite_dev(4, buf, offsets, valid, table, slots, ttl_dec, hit, stream)
+
+
+def nat_ipv6_tcp_rewrite_dev(buf, offsets, valid, table, slots: int, ttl_dec: int = 0, hit=None, stream=None):
+    """The same for IPv6 (36-byte tuples, 80-byte entries; the hop limit is covered by no checksum)."""
+    return _nat_rewrite_dev(6, buf, offsets, valid, table, slots, ttl_dec, hit, stream)
 
 
 def fill_splitmix64_dev(buf, seed: int, byte_off: int = 0, stream=None):
