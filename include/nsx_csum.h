@@ -222,7 +222,10 @@ int nsx_tcp_layout_host(const uint64_t* h_opt_off, const uint64_t* h_data_off, u
  * A frame whose length does not fit its 16-bit length field (IPv4 wire > 65515,
  * IPv6 wire > 65535) is not built: nothing is written for it, padding included,
  * and d_tcp_raw[i] = 0 (a built frame's raw sum is never 0: the pseudo-header
- * holds the byte 6). Validation and conventions as nsx_tcp_build_dev; no
+ * holds the byte 6). That holds for a payload of any length the 64-bit offsets
+ * can say, 2^31 and 2^32 bytes and more included: nsx_tcp_build_dev's limit of
+ * 2^31 bytes per image is a limit on what is built and does not apply to a
+ * frame that is not. Validation and conventions as nsx_tcp_build_dev; no
  * allocation, no host sync, no per-stream counters: the call can be captured
  * into a graph. */
 typedef struct {

@@ -2657,7 +2657,10 @@ __global__ __launch_bounds__(kBlock) void tcp_build_kernel(TcpHdrSoA h, const ui
         uint32_t mpart = partial ? partial[i] : 0u;
         // frame positions: IPH ahead of the TCP header
         const uint32_t mhdr = IPH + 20u + moptlen + (moptlen ? (20u + moptlen) % 4u : 0u);  // tcp.go:118-121
-        const uint32_t mwire = mhdr + (uint32_t)(mde - mdb);                                   // < 2^31
+        // < 2^31: the TCP build's contract. The transmit pass has none ("not built" is its answer to a payload of any
+        // length), so there the length is classified in 64 bits first: capped, it still exceeds the two rows of
+        // the pipelined paths and every IP length field, and such a frame goes to the loop below, which skips it
+        const uint32_t mwire = mhdr + (IPH != 0 ? (uint32_t)min(mde - mdb, (uint64_t)0x20000u) : (uint32_t)(mde - mdb));
         uint32_t mI[kIpDw ? kIpDw : 1];
         uint32_t mskip = 0;  // the TCP length does not fit the IP length field: the frame is not built
         if constexpr (IPH != 0) {
