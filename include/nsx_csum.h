@@ -312,6 +312,146 @@ int nsx_tso_ipv6_tcp_build_dev(const nsx_ip_hdr_soa* ip, const nsx_tcp_hdr_soa* 
                                const uint64_t* d_frame_first, const uint32_t* d_frame_seg, uint64_t n_frames,
                                uint8_t* d_out, const uint64_t* d_out_off, uint16_t* d_tcp_raw, nsx_stream_t stream);
 
+/* UDP (RFC 768; over IPv6 RFC 8200 §8.1): the fused transmit pass, its
+ * segmentation offload and the receive verify for the other transport — the
+ * twins of nsx_tx_*, nsx_tso_* and nsx_rx_* above, as kernels of their own
+ * (csrc/udp_kernels.hip). The checksum is the same computeChecksum sum
+ * (tcp.go:72-95) with three rules TCP does not have: a computed checksum of 0
+ * is sent as 0xFFFF (RFC 768); a received field of 0 means "no checksum" on
+ * IPv4 (RFC 768); a received field of 0 is illegal on IPv6 (RFC 8200 §8.1).
+ * There are device calls only: no _host forms and no sharding; receive
+ * coalescing and the NAT rewrite stay TCP; UDP-Lite, IPv6 zero-checksum tunnels
+ * (RFC 6935) and extension headers are not handled.
+ *
+ * Transmit (nsx_udp_tx_ipv4_build_dev / nsx_udp_tx_ipv6_build_dev): n frames
+ * from the per-frame IP fields of nsx_ip_hdr_soa (as the TCP transmit pass: the
+ * same device arrays, the same NULL defaults), the ports of nsx_udp_hdr_soa
+ * (device arrays, host byte order) and the payload d_data[d_data_off[i],
+ * d_data_off[i+1]) at any source alignment; data_bytes = the extent of d_data.
+ * Frame i is written at d_out + d_out_off[i] under the transmit pass's layout
+ * rule: d_out_off[i] a multiple of 4 with room for the frame rounded up to 4
+ * bytes, the up to 3 bytes after a frame zero-filled, everything else left as
+ * it was. The frame:
+ *   IP header   exactly the one nsx_tx_ipv4_tcp_build_dev /
+ *               nsx_tx_ipv6_tcp_build_dev writes (IPv4: 0x45, 0x00, total
+ *               length, ident, 0x40 0x00, ttl, protocol, header checksum, src,
+ *               dst; IPv6: version 6, tclass, flow, payload length, Next
+ *               Header, hop limit ttl, src, dst), with the protocol / Next
+ *               Header byte 17 and the length that of the UDP datagram (IPv4
+ *               total length 20 + 8 + payload, IPv6 payload length 8 + payload).
+ *   UDP header  8 bytes, big-endian: source port, destination port, length =
+ *               8 + payload, checksum.
+ *   payload     the bytes of d_data, unchanged.
+ * Checksum: raw is the computeChecksum sum over the pseudo-header ‖ the
+ * datagram (UDP header and payload) with the field zero. The IPv4
+ * pseudo-header is src(4) dst(4) 0 17 UDP length(2); the IPv6 one is that of
+ * RFC 8200 §8.1: src(16) dst(16), the UDP length as a 4-byte field, 3 zero
+ * bytes, Next Header 17. The stored field is ~raw, except that 0x0000 is stored
+ * as 0xFFFF. d_udp_raw[i] (nullable) receives raw.
+ * flags: NSX_UDP_NO_CSUM (bit 0, IPv4 only) stores the field 0 ("not computed",
+ * RFC 768) in every frame; d_udp_raw still receives raw. On IPv6 it is
+ * NSX_EINVAL, and so is any other flag bit on either version.
+ * A payload above 65507 bytes (IPv4) or 65527 bytes (IPv6) does not fit the
+ * length fields and is not built: nothing is written for that frame, padding
+ * included, and its raw is 0. A built frame's raw is never 0 (the pseudo-header
+ * holds the byte 17). That holds for any length the 64-bit offsets can say, 2^32
+ * bytes and more included.
+ * nsx_udp_layout_host gives the packed offsets: h_out_off[i] = Σ_{j<i}
+ * round_up4(ip_hdr_len + 8 + len_j), n + 1 entries, ip_hdr_len 20 or 40
+ * (NSX_EINVAL otherwise, for a NULL array and for decreasing offsets; nothing
+ * is written then).
+ * Conventions of the device calls, as the transmit pass: everything is
+ * validated before any launch (NSX_EINVAL: ip or udp NULL, ip->src, ip->dst or
+ * a port array NULL, d_data_off / d_out / d_out_off NULL, d_data NULL with
+ * data_bytes nonzero, a bad flag); n == 0 is NSX_OK without a launch;
+ * NSX_ENODEV without a GPU. No allocation, no host sync, no per-stream
+ * counters: the calls can be captured into a graph.
+ *
+ * Segmentation offload (nsx_udp_uso_ipv4_build_dev / nsx_udp_uso_ipv6_build_dev;
+ * Linux UDP_SEGMENT, __udp_gso_segment): n super-datagrams in, n_frames
+ * datagrams out. Super-datagram s has one entry in every nsx_ip_hdr_soa /
+ * nsx_udp_hdr_soa array, the payload d_data[d_data_off[s], d_data_off[s+1]) of
+ * len_s bytes and d_gso[s] >= 1, the payload bytes per datagram. The frame map
+ * is segmentation offload's own: nsx_tso_count_host(h_data_off, h_gso, n,
+ * h_frame_first) is used as it stands — cnt_s = max(1, ceil(len_s / gso_s)),
+ * frame_first (n + 1) its prefix sum, frame_seg (n_frames) the super-datagram
+ * of each frame, out_off (n_frames + 1) the frame slots.
+ * nsx_udp_uso_layout_host writes h_frame_seg and the packed offsets
+ * nsx_udp_layout_host would give the expanded batch, with nsx_tso_layout_host's
+ * NSX_EINVAL cases: a NULL array, a gso of 0, decreasing offsets, n >= 2^32,
+ * ip_hdr_len other than 20 or 40, and an h_frame_first that is not
+ * nsx_tso_count_host's.
+ * Frame j of s (0 <= j < cnt_s) is exactly the frame nsx_udp_tx_* builds from
+ * s's fields, except:
+ *   payload   d_data[d_data_off[s] + j*gso, min(d_data_off[s] + (j+1)*gso,
+ *             d_data_off[s+1])) — empty when len_s == 0. The kernel reads no
+ *             payload byte outside s's own range, whatever the frame map says
+ *             (j = f - frame_first[frame_seg[f]] modulo 2^64; a slice that would
+ *             start past the range is empty).
+ *   ident     IPv4: (ident[s] + j) modulo 2^16, ident[s] = 0 when the array is
+ *             NULL.
+ * The UDP length, the IP length, the IPv4 header checksum and the UDP checksum
+ * follow from the frame's own slice; ports, addresses, TTL, traffic class and
+ * flow label are copied to every frame. flags, d_udp_raw (n_frames entries)
+ * and the not-built rule as above. The device calls return NSX_OK without a
+ * launch when n_frames == 0; else n == 0, n >= 2^32, n_frames < n and a NULL
+ * d_gso / d_frame_first / d_frame_seg are NSX_EINVAL too.
+ *
+ * Receive verify (nsx_udp_rx_ipv4_verify_dev / nsx_udp_rx_ipv6_verify_dev):
+ * input as nsx_rx_ipv4_tcp_verify_dev — densely packed frames at any alignment,
+ * frame i = d_base[d_offsets[i], d_offsets[i+1]), d_offsets with n + 1 entries.
+ * Bit (i % 64) of d_mask[i / 64] is set iff frame i
+ *   - is well-formed. IPv4: version 4, IHL >= 5, IHL*4 <= frame length, total
+ *     length == frame length, MF clear and fragment offset 0, protocol 17.
+ *     IPv6: at least 48 bytes, version 6, 40 + payload length == frame length,
+ *     Next Header 17 (extension headers are not walked). Both: with P the IP
+ *     payload length (frame length less the IP header) and U the UDP length
+ *     field, 8 <= U <= P. Bytes past U are padding and are ignored, as Linux
+ *     trims them;
+ *   - IPv4 only: has a valid header checksum — raw over the IHL*4 header bytes
+ *     is 0xFFFF;
+ *   - has a valid UDP checksum: raw is taken over the pseudo-header built from
+ *     the frame's own addresses, 17 and U ‖ the first U bytes of the datagram;
+ *     raw == 0xFFFF verifies. On IPv4 a checksum field of 0 also verifies,
+ *     whatever raw is. On IPv6 a field of 0 does not verify, whatever raw is.
+ * d_ip_raw (IPv4, nullable) is as in the TCP pass: the header's raw sum, 0 when
+ * the frame holds fewer than 20 bytes, IHL < 5 or IHL*4 exceeds the frame.
+ * d_udp_raw (nullable) is that raw, 0 unless the frame is well-formed. Bits
+ * past n in the last word are 0; d_mask holds ceil(n/64) words. No byte outside
+ * a frame's own range is read. The split over the GPU's waves is static — a wave
+ * per mask word, no per-stream deal counters — so the call can be captured into
+ * a graph on any stream. n == 0 is NSX_OK without a launch; a NULL d_base,
+ * d_offsets or d_mask is NSX_EINVAL; NSX_ENODEV without a GPU. */
+typedef struct {
+    const uint16_t* src_port;  /* n entries, host byte order */
+    const uint16_t* dst_port;
+} nsx_udp_hdr_soa;             /* device arrays */
+#define NSX_UDP_NO_CSUM 1u     /* flags bit 0, IPv4 only: send checksum field 0 ("not computed", RFC 768) */
+
+int nsx_udp_layout_host(const uint64_t* h_data_off, uint64_t n, uint32_t ip_hdr_len, uint64_t* h_out_off);
+int nsx_udp_uso_layout_host(const uint64_t* h_data_off, const uint32_t* h_gso, const uint64_t* h_frame_first,
+                            uint64_t n, uint32_t ip_hdr_len, uint32_t* h_frame_seg, uint64_t* h_out_off);
+int nsx_udp_tx_ipv4_build_dev(const nsx_ip_hdr_soa* ip, const nsx_udp_hdr_soa* udp, const uint8_t* d_data,
+                              const uint64_t* d_data_off, uint64_t data_bytes, uint64_t n, uint32_t flags,
+                              uint8_t* d_out, const uint64_t* d_out_off, uint16_t* d_udp_raw, nsx_stream_t stream);
+int nsx_udp_tx_ipv6_build_dev(const nsx_ip_hdr_soa* ip, const nsx_udp_hdr_soa* udp, const uint8_t* d_data,
+                              const uint64_t* d_data_off, uint64_t data_bytes, uint64_t n, uint32_t flags,
+                              uint8_t* d_out, const uint64_t* d_out_off, uint16_t* d_udp_raw, nsx_stream_t stream);
+int nsx_udp_uso_ipv4_build_dev(const nsx_ip_hdr_soa* ip, const nsx_udp_hdr_soa* udp, const uint8_t* d_data,
+                               const uint64_t* d_data_off, uint64_t data_bytes, const uint32_t* d_gso, uint64_t n,
+                               const uint64_t* d_frame_first, const uint32_t* d_frame_seg, uint64_t n_frames,
+                               uint32_t flags, uint8_t* d_out, const uint64_t* d_out_off, uint16_t* d_udp_raw,
+                               nsx_stream_t stream);
+int nsx_udp_uso_ipv6_build_dev(const nsx_ip_hdr_soa* ip, const nsx_udp_hdr_soa* udp, const uint8_t* d_data,
+                               const uint64_t* d_data_off, uint64_t data_bytes, const uint32_t* d_gso, uint64_t n,
+                               const uint64_t* d_frame_first, const uint32_t* d_frame_seg, uint64_t n_frames,
+                               uint32_t flags, uint8_t* d_out, const uint64_t* d_out_off, uint16_t* d_udp_raw,
+                               nsx_stream_t stream);
+int nsx_udp_rx_ipv4_verify_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n, uint64_t* d_mask,
+                               uint16_t* d_ip_raw, uint16_t* d_udp_raw, nsx_stream_t stream);
+int nsx_udp_rx_ipv6_verify_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n, uint64_t* d_mask,
+                               uint16_t* d_udp_raw, nsx_stream_t stream);
+
 /* IPv4 header checksums (RFC 791 §3.1; SURVEY.md §8 f3 — the reference has no
  * IPv4 header codec, network/ip/v4/ipv4.go holds addresses only). Packet i's
  * header starts at d_base + i*stride + hdr_off (any alignment) and is IHL*4

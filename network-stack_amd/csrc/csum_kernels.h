@@ -1,6 +1,6 @@
-// csum_kernels.h — internal launcher interface between the C ABI (csum_api.cpp, nat_api.cpp,
+// csum_kernels.h — internal launcher interface between the C ABI (csum_api.cpp, nat_api.cpp, udp_api.cpp,
 // host_batch.cpp) and the gfx950 kernels (csum_kernels.hip, gro_kernels.hip, gro_flow_kernels.hip,
-// nat_kernels.hip). Not a public header.
+// nat_kernels.hip, udp_kernels.hip). Not a public header.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -137,6 +137,23 @@ hipError_t launch_gro_flow(const LaunchCfg& c, int ipver, const void* d_base, co
 // slots a power of two <= 2^31, the table 16-byte aligned, ttl_dec <= 255 (nat_api.cpp checks all of it).
 hipError_t launch_nat_rewrite(int ipver, void* d_base, const uint64_t* d_offsets, uint64_t n, const uint64_t* valid,
                               const void* d_table, uint64_t slots, uint32_t ttl_dec, uint64_t* d_hit, hipStream_t st);
+// The UDP passes (nsx_udp_*, udp_kernels.hip). The frame map of segmentation offload over per-super-datagram arrays:
+struct UdpUsoMap {
+    const uint32_t* gso;          // per super-datagram: payload bytes per datagram
+    const uint64_t* frame_first;  // per super-datagram: its first frame
+    const uint32_t* frame_seg;    // per frame: its super-datagram
+};
+// Whole IPv4 / IPv6 datagrams carrying UDP (ipver 4 / 6), n_frames of them; uso null: one entry per frame in every
+// array (n_super unused), else one per super-datagram (n_super >= 1 of them). c.run_segs = frames per wave task
+// (1..64), c.blocks_per_cu the grid (default 4). One launch; none for n_frames == 0.
+hipError_t launch_udp_build(const LaunchCfg& c, int ipver, const IpHdrSoA& ip, const uint16_t* src_port,
+                            const uint16_t* dst_port, const UdpUsoMap* uso, uint64_t n_super, const uint8_t* data,
+                            const uint64_t* data_off, uint64_t data_bytes, uint64_t n_frames, uint32_t no_csum,
+                            uint8_t* out, const uint64_t* out_off, uint16_t* raw, hipStream_t st);
+// The UDP receive verify: a wave per 64-frame mask word, statically split; c.run_segs = frames per metadata step
+// (1..64, default 16), c.blocks_per_cu the grid (default 8). ip_raw (IPv4 only) / udp_raw nullable.
+hipError_t launch_udp_rx(const LaunchCfg& c, int ipver, const void* d_base, const uint64_t* d_offsets, uint64_t n,
+                         uint64_t* mask, uint16_t* ip_raw, uint16_t* udp_raw, hipStream_t st);
 struct TcpParsedSoA {  // device arrays, one entry per segment; every member nullable
     uint16_t* src_port;
     uint16_t* dst_port;

@@ -196,6 +196,34 @@ bool tso_layout_ok(uint32_t iph, const uint64_t* opt_off, const uint64_t* data_o
     });
 }
 
+// ---- the UDP passes' layouts ----
+bool udp_layout(uint32_t iph, const uint64_t* data_off, uint64_t n, uint64_t* out_off) {
+    for (uint64_t i = 0; i < n; ++i)
+        if (data_off[i + 1] < data_off[i]) return false;  // everything checked before anything is written
+    uint64_t at = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        out_off[i] = at;
+        at += udp_slot(iph, data_off[i + 1] - data_off[i]);
+    }
+    out_off[n] = at;
+    return true;
+}
+
+uint64_t udp_uso_layout(uint32_t iph, const uint64_t* data_off, const uint32_t* gso, uint64_t n, uint32_t* frame_seg,
+                        uint64_t* out_off) {
+    uint64_t f = 0, at = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t len = data_off[i + 1] - data_off[i], cnt = tso_frames(len, gso[i]);
+        for (uint64_t k = 0; k < cnt; ++k, ++f) {
+            frame_seg[f] = (uint32_t)i;
+            out_off[f] = at;
+            at += udp_slot(iph, std::min<uint64_t>(gso[i], len - k * gso[i]));
+        }
+    }
+    out_off[f] = at;
+    return f;
+}
+
 // ---- the NAT rewrite's translation table ----
 uint32_t nat_hash(const uint8_t* t, uint32_t tuple_bytes) {
     uint32_t h = 0x811C9DC5u;
@@ -276,6 +304,23 @@ int nsx_tso_layout_host(const uint64_t* h_opt_off, const uint64_t* h_data_off, c
         return true;
     });
     h_out_off[frames] = at;
+    return NSX_OK;
+}
+
+int nsx_udp_layout_host(const uint64_t* h_data_off, uint64_t n, uint32_t ip_hdr_len, uint64_t* h_out_off) {
+    if ((ip_hdr_len != 20 && ip_hdr_len != 40) || !h_out_off || (n && !h_data_off)) return NSX_EINVAL;
+    return nsx::udp_layout(ip_hdr_len, h_data_off, n, h_out_off) ? NSX_OK : NSX_EINVAL;
+}
+
+int nsx_udp_uso_layout_host(const uint64_t* h_data_off, const uint32_t* h_gso, const uint64_t* h_frame_first,
+                            uint64_t n, uint32_t ip_hdr_len, uint32_t* h_frame_seg, uint64_t* h_out_off) {
+    if ((ip_hdr_len != 20 && ip_hdr_len != 40) || !h_out_off || !h_frame_first || n >= (1ull << 32) ||
+        (n && (!h_data_off || !h_gso)))
+        return NSX_EINVAL;
+    // everything checked before anything is written: the map must be nsx_tso_count_host's
+    const uint64_t frames = nsx::tso_walk(nullptr, h_data_off, h_gso, n, h_frame_first, nullptr);
+    if (frames == nsx::kTsoBad || (frames && !h_frame_seg)) return NSX_EINVAL;
+    nsx::udp_uso_layout(ip_hdr_len, h_data_off, h_gso, n, h_frame_seg, h_out_off);
     return NSX_OK;
 }
 

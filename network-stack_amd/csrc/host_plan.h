@@ -82,6 +82,16 @@ bool tso_layout_ok(uint32_t ip_hdr_len, const uint64_t* opt_off, const uint64_t*
                    uint64_t n, const uint32_t* frame_seg, const uint64_t* out_off, uint64_t n_frames,
                    uint64_t* seg_out, bool* gaps);
 
+// ---- the UDP passes' layouts (include/nsx_csum.h nsx_udp_layout_host / nsx_udp_uso_layout_host) ----
+// The 4-padded slot of a UDP frame: IP header, the 8-byte UDP header, the payload.
+inline uint64_t udp_slot(uint32_t ip_hdr_len, uint64_t payload) { return (ip_hdr_len + 8u + payload + 3u) & ~3ull; }
+// Packed slots of n frames into out_off (n + 1); false, with nothing written, for decreasing offsets.
+bool udp_layout(uint32_t ip_hdr_len, const uint64_t* data_off, uint64_t n, uint64_t* out_off);
+// frame_seg and the packed slots of a walked frame map (tso_walk: the map is segmentation offload's own) over its
+// cuts of gso payload bytes; returns the frame count.
+uint64_t udp_uso_layout(uint32_t ip_hdr_len, const uint64_t* data_off, const uint32_t* gso, uint64_t n,
+                        uint32_t* frame_seg, uint64_t* out_off);
+
 // ---- the NAT rewrite's translation table (include/nsx_csum.h nsx_nat_*) ----
 // Tuple and entry bytes per IP version: 12 / 32 (IPv4), 36 / 80 (IPv6). An entry: match tuple, state dword
 // (little-endian, 1 = occupied), new tuple, zero dword.

@@ -141,13 +141,27 @@ def lib() -> ctypes.CDLL:
             "nsx_nat_table_build_host": [u32, vp, vp, u64, vp, u64],
             "nsx_nat_ipv4_tcp_rewrite_dev": [vp, vp, u64, vp, vp, u64, u32, vp, vp],
             "nsx_nat_ipv6_tcp_rewrite_dev": [vp, vp, u64, vp, vp, u64, u32, vp, vp],
+            "nsx_udp_layout_host": [vp, u64, u32, vp],
+            "nsx_udp_uso_layout_host": [vp, vp, vp, u64, u32, vp, vp],
+            "nsx_udp_tx_ipv4_build_dev": [vp, vp, vp, vp, u64, u64, u32, vp, vp, vp, vp],
+            "nsx_udp_tx_ipv6_build_dev": [vp, vp, vp, vp, u64, u64, u32, vp, vp, vp, vp],
+            "nsx_udp_tx_ipv4_build_dev_tuned": [vp, vp, vp, vp, u64, u64, u32, vp, vp, vp, vp, vp],
+            "nsx_udp_tx_ipv6_build_dev_tuned": [vp, vp, vp, vp, u64, u64, u32, vp, vp, vp, vp, vp],
+            "nsx_udp_uso_ipv4_build_dev": [vp, vp, vp, vp, u64, vp, u64, vp, vp, u64, u32, vp, vp, vp, vp],
+            "nsx_udp_uso_ipv6_build_dev": [vp, vp, vp, vp, u64, vp, u64, vp, vp, u64, u32, vp, vp, vp, vp],
+            "nsx_udp_uso_ipv4_build_dev_tuned": [vp, vp, vp, vp, u64, vp, u64, vp, vp, u64, u32, vp, vp, vp, vp, vp],
+            "nsx_udp_uso_ipv6_build_dev_tuned": [vp, vp, vp, vp, u64, vp, u64, vp, vp, u64, u32, vp, vp, vp, vp, vp],
+            "nsx_udp_rx_ipv4_verify_dev": [vp, vp, u64, vp, vp, vp, vp],
+            "nsx_udp_rx_ipv4_verify_dev_tuned": [vp, vp, u64, vp, vp, vp, vp, vp],
+            "nsx_udp_rx_ipv6_verify_dev": [vp, vp, u64, vp, vp, vp],
+            "nsx_udp_rx_ipv6_verify_dev_tuned": [vp, vp, u64, vp, vp, vp, vp],
             "nsx_fixed_launch_count": [u64, u32, u64, vp, ctypes.POINTER(u64)],
             "nsx_ipv4_hdr_launch_count": [vp, u64, u32, u64, vp, ctypes.POINTER(u64)],
         }
         # present since ABI round 6, and the transmit pass since its own change; an older library (same-box A/B against a
         # previous build) lacks them
         optional = {"nsx_stream_release", "nsx_deal_sets_in_use"} | \
-            {k for k in sig if k.startswith(("nsx_tx_", "nsx_tso_", "nsx_gro_", "nsx_nat_"))}
+            {k for k in sig if k.startswith(("nsx_tx_", "nsx_tso_", "nsx_gro_", "nsx_nat_", "nsx_udp_"))}
         for name, args in sig.items():
             if name in optional and not hasattr(L, name):
                 continue
@@ -1141,6 +1155,162 @@ def nat_ipv4_tcp_rewrite_dev(buf, offsets, valid, table, slots: int, ttl_dec: in
 def nat_ipv6_tcp_rewrite_dev(buf, offsets, valid, table, slots: int, ttl_dec: int = 0, hit=None, stream=None):
     """The same for IPv6 (36-byte tuples, 80-byte entries; the hop limit is covered by no checksum)."""
     return _nat_rewrite_dev(6, buf, offsets, valid, table, slots, ttl_dec, hit, stream)
+
+
+# ---------------------------------------------------------------------------
+# UDP: fused transmit pass, segmentation offload and receive verify (nsx_udp_*)
+# ---------------------------------------------------------------------------
+UDP_NO_CSUM = 1  # NSX_UDP_NO_CSUM
+UDP_FIELDS = ("src_port", "dst_port")  # nsx_udp_hdr_soa members, 2-byte elements
+
+
+class UdpHdrSoA(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name in UDP_FIELDS]
+
+
+def udp_layout_host(data_off: np.ndarray, ip_hdr_len: int = 20) -> np.ndarray:
+    """nsx_udp_layout_host: packed 4-aligned frame offsets, out_off[i] = Σ_{j<i} round_up4(ip_hdr_len + 8 + len_j)."""
+    data_off = np.ascontiguousarray(data_off, np.uint64)
+    n = data_off.size - 1
+    if n < 0:
+        raise ValueError("udp_layout_host data_off: needs n + 1 entries")
+    out = np.zeros(n + 1, np.uint64)
+    _check(lib().nsx_udp_layout_host(_np_ptr(data_off), n, ip_hdr_len, _np_ptr(out)), "nsx_udp_layout_host")
+    return out
+
+
+def udp_uso_layout_host(data_off: np.ndarray, gso: np.ndarray, frame_first: np.ndarray, ip_hdr_len: int = 20):
+    """nsx_udp_uso_layout_host: (frame_seg[n_frames], out_off[n_frames + 1]) over tso_count_host's frame map."""
+    data_off, gso, n = _tso_host_args(data_off, gso, "udp_uso_layout_host")
+    first = np.ascontiguousarray(frame_first, np.uint64)
+    if first.size < n + 1:
+        raise ValueError(f"udp_uso_layout_host frame_first: {first.size} entries for {n} super-datagrams")
+    # the C call checks frame_first against its own count before it writes: these sizes hold whenever it writes
+    nf = int(first[n])
+    if nf >= 1 << 40:
+        raise ValueError(f"udp_uso_layout_host frame_first: {nf} frames")
+    seg = np.zeros(max(nf, 1), np.uint32)
+    out = np.zeros(nf + 1, np.uint64)
+    _check(lib().nsx_udp_uso_layout_host(_np_ptr(data_off), _np_ptr(gso), _np_ptr(first), n, ip_hdr_len, _np_ptr(seg),
+                                         _np_ptr(out)), "nsx_udp_uso_layout_host")
+    return seg[:nf], out
+
+
+def _udp_soa(what: str, ipver: int, ip: dict, ports: dict, n: int):
+    sizes = _ip_sizes(ipver)
+    for k in ("src", "dst"):
+        if ip.get(k) is None:
+            raise ValueError(f"{what}: address array {k!r} missing")
+    for k in IP_FIELDS:
+        _span(ip.get(k), sizes[k] * n, f"{what} {k}", elem=None if k in ("src", "dst") else sizes[k])
+    for k in UDP_FIELDS:
+        if ports.get(k) is None:
+            raise ValueError(f"{what}: header field {k!r} missing")
+        _span(ports.get(k), 2 * n, f"{what} {k}", elem=2)
+
+
+def _udp_tx_build_dev(ipver: int, ip: dict, ports: dict, data, data_off, out, out_off, flags, raw, stream, tune):
+    what = f"udp_tx_ipv{ipver}_build_dev"
+    n = _count(data_off, f"{what} data_off")
+    _udp_soa(what, ipver, ip, ports, n)
+    _span(data, 0, f"{what} data")
+    _span(out_off, 8 * (n + 1), f"{what} out_off", elem=8)
+    # the frame lengths are in device memory; the least n frames can take is an IP and a UDP header each
+    _span(out, max(n, 0) * (28 if ipver == 4 else 48), f"{what} out", elem=1)
+    _span(raw, 2 * n, f"{what} raw", elem=2)
+    ipsoa = IpHdrSoA(*[_dev_ptr(ip.get(k)) for k in IP_FIELDS])
+    soa = UdpHdrSoA(*[_dev_ptr(ports.get(k)) for k in UDP_FIELDS])
+    fn = getattr(lib(), f"nsx_udp_tx_ipv{ipver}_build_dev_tuned")
+    _check(fn(ctypes.byref(ipsoa), ctypes.byref(soa), _dev_ptr(data), _dev_ptr(data_off), data.numel(), n, int(flags),
+              _dev_ptr(out), _dev_ptr(out_off), _dev_ptr(raw), _stream(stream), _tune(tune)), f"nsx_{what}")
+    return out
+
+
+def udp_tx_ipv4_build_dev(ip: dict, ports: dict, data, data_off, out, out_off, flags: int = 0, raw=None, stream=None,
+                          tune=None):
+    """UDP transmit pass: whole IPv4 datagrams carrying UDP (header checksum and UDP checksum in place) at out +
+    out_off[i]. ip as tx_ipv4_tcp_build_dev; ports: dict of device tensors src_port, dst_port (2 B per frame);
+    flags: UDP_NO_CSUM stores the field 0; raw (optional) receives the UDP raw sums."""
+    return _udp_tx_build_dev(4, ip, ports, data, data_off, out, out_off, flags, raw, stream, tune)
+
+
+def udp_tx_ipv6_build_dev(ip: dict, ports: dict, data, data_off, out, out_off, flags: int = 0, raw=None, stream=None,
+                          tune=None):
+    """The same for IPv6 (no flag is valid there)."""
+    return _udp_tx_build_dev(6, ip, ports, data, data_off, out, out_off, flags, raw, stream, tune)
+
+
+def _udp_uso_build_dev(ipver: int, ip: dict, ports: dict, data, data_off, gso, frame_first, frame_seg, out, out_off,
+                       flags, raw, stream, tune, n_frames):
+    what = f"udp_uso_ipv{ipver}_build_dev"
+    n = _count(data_off, f"{what} data_off")
+    nf = _count(out_off, f"{what} out_off") if n_frames is None else int(n_frames)
+    if nf < 0:
+        raise ValueError(f"{what}: n_frames {nf}")
+    _span(frame_seg, 4 * nf, f"{what} frame_seg", elem=4)
+    _udp_soa(what, ipver, ip, ports, n)
+    _span(data, 0, f"{what} data")
+    _span(gso, 4 * n, f"{what} gso", elem=4)
+    _span(frame_first, 8 * (n + 1), f"{what} frame_first", elem=8)
+    _span(out_off, 8 * (nf + 1), f"{what} out_off", elem=8)
+    if nf and (n <= 0 or nf < n):
+        raise ValueError(f"{what}: {nf} frames for {n} super-datagrams")
+    _span(out, nf * (28 if ipver == 4 else 48), f"{what} out", elem=1)
+    _span(raw, 2 * nf, f"{what} raw", elem=2)
+    ipsoa = IpHdrSoA(*[_dev_ptr(ip.get(k)) for k in IP_FIELDS])
+    soa = UdpHdrSoA(*[_dev_ptr(ports.get(k)) for k in UDP_FIELDS])
+    fn = getattr(lib(), f"nsx_udp_uso_ipv{ipver}_build_dev_tuned")
+    _check(fn(ctypes.byref(ipsoa), ctypes.byref(soa), _dev_ptr(data), _dev_ptr(data_off), data.numel(), _dev_ptr(gso),
+              max(n, 0), _dev_ptr(frame_first), _dev_ptr(frame_seg), nf, int(flags), _dev_ptr(out), _dev_ptr(out_off),
+              _dev_ptr(raw), _stream(stream), _tune(tune)), f"nsx_{what}")
+    return out
+
+
+def udp_uso_ipv4_build_dev(ip: dict, ports: dict, data, data_off, gso, frame_first, frame_seg, out, out_off,
+                           flags: int = 0, raw=None, stream=None, tune=None, n_frames=None):
+    """UDP segmentation offload: ip, ports, data_off and gso (uint32: payload bytes per datagram) hold one entry per
+    super-datagram; frame_first / frame_seg / out_off are the frame map of tso_count_host and udp_uso_layout_host as
+    device tensors (n_frames defaults to out_off's length less one). Frame j carries ident + j."""
+    return _udp_uso_build_dev(4, ip, ports, data, data_off, gso, frame_first, frame_seg, out, out_off, flags, raw,
+                              stream, tune, n_frames)
+
+
+def udp_uso_ipv6_build_dev(ip: dict, ports: dict, data, data_off, gso, frame_first, frame_seg, out, out_off,
+                           flags: int = 0, raw=None, stream=None, tune=None, n_frames=None):
+    """The same for IPv6."""
+    return _udp_uso_build_dev(6, ip, ports, data, data_off, gso, frame_first, frame_seg, out, out_off, flags, raw,
+                              stream, tune, n_frames)
+
+
+def udp_rx_ipv4_verify_dev(buf, offsets, mask=None, ip_raw=None, udp_raw=None, stream=None, tune=None):
+    """UDP receive verify over packed IPv4/UDP frames: validity bitmask (+ optional raw sums)."""
+    import torch
+    n = _count(offsets, "udp_rx_ipv4_verify_dev offsets")
+    if mask is None:
+        mask = torch.empty((max(n, 0) + 63) // 64, dtype=torch.int64, device=offsets.device)  # u64 bits
+    _span(buf, 0, "udp_rx_ipv4_verify_dev buf")
+    _span(mask, 8 * ((n + 63) // 64), "udp_rx_ipv4_verify_dev mask", elem=8)
+    _span(ip_raw, 2 * n, "udp_rx_ipv4_verify_dev ip_raw", elem=2)
+    _span(udp_raw, 2 * n, "udp_rx_ipv4_verify_dev udp_raw", elem=2)
+    _check(lib().nsx_udp_rx_ipv4_verify_dev_tuned(_dev_ptr(buf), _dev_ptr(offsets), n, _dev_ptr(mask),
+                                                  _dev_ptr(ip_raw), _dev_ptr(udp_raw), _stream(stream), _tune(tune)),
+           "nsx_udp_rx_ipv4_verify_dev")
+    return mask
+
+
+def udp_rx_ipv6_verify_dev(buf, offsets, mask=None, udp_raw=None, stream=None, tune=None):
+    """UDP receive verify over packed IPv6/UDP packets: validity bitmask (+ optional raw sums)."""
+    import torch
+    n = _count(offsets, "udp_rx_ipv6_verify_dev offsets")
+    if mask is None:
+        mask = torch.empty((max(n, 0) + 63) // 64, dtype=torch.int64, device=offsets.device)  # u64 bits
+    _span(buf, 0, "udp_rx_ipv6_verify_dev buf")
+    _span(mask, 8 * ((n + 63) // 64), "udp_rx_ipv6_verify_dev mask", elem=8)
+    _span(udp_raw, 2 * n, "udp_rx_ipv6_verify_dev udp_raw", elem=2)
+    _check(lib().nsx_udp_rx_ipv6_verify_dev_tuned(_dev_ptr(buf), _dev_ptr(offsets), n, _dev_ptr(mask),
+                                                  _dev_ptr(udp_raw), _stream(stream), _tune(tune)),
+           "nsx_udp_rx_ipv6_verify_dev")
+    return mask
 
 
 def fill_splitmix64_dev(buf, seed: int, byte_off: int = 0, stream=None):
