@@ -320,7 +320,8 @@ int nsx_tso_ipv6_tcp_build_dev(const nsx_ip_hdr_soa* ip, const nsx_tcp_hdr_soa* 
  * is sent as 0xFFFF (RFC 768); a received field of 0 means "no checksum" on
  * IPv4 (RFC 768); a received field of 0 is illegal on IPv6 (RFC 8200 §8.1).
  * There are device calls only: no _host forms and no sharding; receive
- * coalescing and the NAT rewrite stay TCP; UDP-Lite, IPv6 zero-checksum tunnels
+ * coalescing is nsx_ugro_* below (UDP receive coalescing), the NAT rewrite stays
+ * TCP; UDP-Lite, IPv6 zero-checksum tunnels
  * (RFC 6935) and extension headers are not handled.
  *
  * Transmit (nsx_udp_tx_ipv4_build_dev / nsx_udp_tx_ipv6_build_dev): n frames
@@ -688,6 +689,126 @@ int
 nsx_gro_flow_ipv6_tcp_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n, const uint64_t* d_valid,
                           uint32_t* d_order, const nsx_gro_out* out, void* d_work, uint64_t work_bytes,
                           nsx_stream_t stream);
+
+/* UDP receive coalescing (Linux UDP_GRO), the inverse of UDP segmentation
+ * offload: the datagrams of a receive batch in, super-datagrams out — per run of
+ * consecutive datagrams of one flow one set of header fields and one contiguous
+ * payload run, in exactly the arrays nsx_udp_uso_ipv4_build_dev /
+ * nsx_udp_uso_ipv6_build_dev take. nsx_ugro_ipv4_dev / nsx_ugro_ipv6_dev
+ * coalesce by adjacency, as nsx_gro_* does for TCP; nsx_ugro_flow_ipv4_dev /
+ * nsx_ugro_flow_ipv6_dev coalesce per flow, as nsx_gro_flow_* does. Kernels of
+ * their own (csrc/ugro_kernels.hip); the TCP calls are untouched.
+ *
+ * Input as nsx_gro_*: d_base, d_offsets (n + 1 entries), n, and d_valid, the
+ * bitmask of nsx_udp_rx_ipv4_verify_dev / nsx_udp_rx_ipv6_verify_dev over the
+ * same frames (required).
+ *
+ * UDP member. Frame i is a member iff its d_valid bit is set; it is well-formed
+ * as the UDP receive verify defines (version, lengths, protocol / Next Header
+ * 17, no fragment, and with P the IP payload length and U the UDP length field,
+ * 8 <= U <= P — re-checked here, so a wrong mask never makes a kernel read
+ * outside the frame's own byte range, and a frame whose bit is clear is not
+ * read at all); U == P, no padding past the UDP length; and its UDP checksum
+ * field is not 0 (Linux udp_gro_receive_segment also requires a nonzero
+ * checksum, "for symmetry with GSO"). A non-member belongs to no
+ * super-datagram: its frame_seg is 0xFFFFFFFF and it breaks runs. For a member
+ * pay_i = U - 8.
+ *
+ * UDP same(i, i-1), purely pairwise, holds iff both frames are members; src,
+ * dst and TTL / hop limit are equal; IPv4: both have IHL 5, equal TOS, equal
+ * bytes 6-7, and ident_i == ident_{i-1} + 1 mod 2^16; IPv6: the first 4 header
+ * bytes (version, class, flow) are equal; and both UDP ports are equal.
+ *
+ * join(i) is the three-frame window of nsx_gro_*, word for word: it holds iff
+ * same(i, i-1), 1 <= pay_i <= pay_{i-1}, and NOT (i >= 2 and same(i-1, i-2) and
+ * pay_{i-1} < pay_{i-2}). Every datagram of a run but the last therefore has
+ * the same payload length (1000, 800, 600, 400, 200 gives [1000, 800], [600],
+ * [400], [200]). A member that does not join is a head; super-datagrams are
+ * numbered in frame order; n_super = the number of heads. There is no
+ * 64-datagram cap and no 64 KiB cap on a super-datagram, unlike Linux's
+ * UDP_GRO_CNT_MAX: it has no length field.
+ *
+ * Every member of nsx_ugro_out is a writable device array and required. For
+ * super-datagram s with first frame f and last frame l, all written:
+ *   src, dst, ident (IPv4; 0 for IPv6), ttl, tclass (IPv4: the TOS byte), flow
+ *     (IPv6; 0 for IPv4), src_port and dst_port from f, exactly as nsx_gro_out
+ *     takes them from f — n x 4 (IPv4) or n x 16 (IPv6) address bytes;
+ *   gso[s] = max(pay_f, 1);
+ *   data[data_off[s], data_off[s+1]) = the payloads of f..l back to back;
+ *   first_frame[s] = f; frame_cnt[s] = l - f + 1.
+ * data_off[0] = 0 and the offsets are packed without gaps (n_super + 1 entries).
+ * frame_seg[i] = frame i's super-datagram, 0xFFFFFFFF for a non-member.
+ * *n_super is a uint64_t in device memory. Entries at index >= n_super, offset
+ * entries past n_super, and data bytes past the last offset are left exactly
+ * as they were. Worst-case extents: n entries per array, n + 1 offsets,
+ * d_offsets[n] - d_offsets[0] data bytes.
+ *
+ * Flow-keyed form, related to the adjacent form exactly as nsx_gro_flow_* is to
+ * nsx_gro_*: the UDP flow key is FNV-1a as defined there (h = 0x811C9DC5; for
+ * each dword w, h = ((h ^ w) * 0x01000193) mod 2^32) over the little-endian
+ * address dwords (IPv4 header bytes 12-19, IPv6 header bytes 8-39), then the
+ * dword holding the two UDP ports (UDP bytes 0-3); a non-member gets
+ * 0xFFFFFFFF. Of a frame whose bit is set at most the IP header and the 8 UDP
+ * header bytes are read for the key. d_order (n entries, an output) is the
+ * stable ascending sort of the frame indices by key, bit for bit
+ * numpy.argsort(keys, kind="stable"); the rules above run over that order;
+ * first_frame[s] is a position in d_order; frame_seg stays indexed by the
+ * original frame (frame_seg[d_order[p]] = frame_seg'[p]). A key collision
+ * costs merges and never merges wrongly. nsx_ugro_flow_work_bytes(n) >=
+ * nsx_ugro_work_bytes(n) for every tune setting.
+ *
+ * The defining property of UDP coalescing: for frames the UDP transmit pass can
+ * express (IPv4 with IHL 5, bytes 6-7 == 0x40 0x00 and TOS 0; any IPv6 member),
+ * the outputs go straight into nsx_udp_uso_ipv4_build_dev /
+ * nsx_udp_uso_ipv6_build_dev with flags 0 (frame_first = the prefix sum of
+ * frame_cnt; frame_seg as it stands for the adjacent form over a batch of
+ * members, gathered through d_order for the flow-keyed one) and rebuild every
+ * member frame byte for byte, the UDP checksum included: a verified nonzero
+ * field is exactly what the transmit pass stores, 0xFFFF where the field-zero
+ * raw sum is 0xFFFF. IPv4 options, a clear DF bit and a nonzero TOS are lost,
+ * as for TCP. A datagram whose IPv4 checksum field is 0 is valid to the verify
+ * but could not be rebuilt by a pass that computes checksums, so it stays a
+ * non-member; so does a padded datagram.
+ *
+ * Validation and conventions as nsx_gro_* and nsx_gro_flow_*: NSX_EINVAL before
+ * any launch for a NULL pointer or struct member, n >= 2^32 - 1, or work_bytes
+ * too small (d_base and d_valid, and d_order for the flow-keyed form, may be
+ * NULL when n == 0); then NSX_ENODEV without a GPU. n == 0 writes *n_super = 0
+ * and data_off[0] = 0 on the stream and does not write d_order. No allocation,
+ * no host sync, no per-stream counters: each call is one serial chain of
+ * launches and can be captured into a graph. 64-bit offsets throughout: frames
+ * may lie past 2^32 in d_base. There are no _host forms and no sharding. The
+ * _tuned twins are in nsx_ugro_tune.h. */
+typedef struct {
+    uint64_t* n_super;
+    uint8_t*  src;          /* nsx_ip_hdr_soa members */
+    uint8_t*  dst;
+    uint16_t* ident;
+    uint8_t*  ttl;
+    uint8_t*  tclass;
+    uint32_t* flow;
+    uint16_t* src_port;     /* nsx_udp_hdr_soa members */
+    uint16_t* dst_port;
+    uint32_t* gso;
+    uint8_t*  data;
+    uint64_t* data_off;
+    uint64_t* first_frame;
+    uint32_t* frame_cnt;
+    uint32_t* frame_seg;    /* per frame */
+} nsx_ugro_out;
+
+int nsx_ugro_work_bytes(uint64_t n, uint64_t* out);
+int nsx_ugro_flow_work_bytes(uint64_t n, uint64_t* out);
+int nsx_ugro_ipv4_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n, const uint64_t* d_valid,
+                      const nsx_ugro_out* out, void* d_work, uint64_t work_bytes, nsx_stream_t stream);
+int nsx_ugro_ipv6_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n, const uint64_t* d_valid,
+                      const nsx_ugro_out* out, void* d_work, uint64_t work_bytes, nsx_stream_t stream);
+int nsx_ugro_flow_ipv4_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n, const uint64_t* d_valid,
+                           uint32_t* d_order, const nsx_ugro_out* out, void* d_work, uint64_t work_bytes,
+                           nsx_stream_t stream);
+int nsx_ugro_flow_ipv6_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n, const uint64_t* d_valid,
+                           uint32_t* d_order, const nsx_ugro_out* out, void* d_work, uint64_t work_bytes,
+                           nsx_stream_t stream);
 
 /* In-place NAT rewrite with incremental checksum update (RFC 1071 §2(4),
  * RFC 1624): the frames of a receive batch, that pass's validity mask and a

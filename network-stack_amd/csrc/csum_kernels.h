@@ -1,6 +1,6 @@
 // csum_kernels.h — internal launcher interface between the C ABI (csum_api.cpp, nat_api.cpp, udp_api.cpp,
-// host_batch.cpp) and the gfx950 kernels (csum_kernels.hip, gro_kernels.hip, gro_flow_kernels.hip,
-// nat_kernels.hip, udp_kernels.hip). Not a public header.
+// ugro_api.cpp, host_batch.cpp) and the gfx950 kernels (csum_kernels.hip, gro_kernels.hip, gro_flow_kernels.hip,
+// nat_kernels.hip, udp_kernels.hip, ugro_kernels.hip). Not a public header.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -133,6 +133,48 @@ uint64_t gro_flow_work_bytes(uint64_t n);
 // 1..64).
 hipError_t launch_gro_flow(const LaunchCfg& c, int ipver, const void* d_base, const uint64_t* d_offsets, uint64_t n,
                            const uint64_t* valid, uint32_t* d_order, const GroOut& o, void* work, hipStream_t st);
+// The stable radix sort of launch_gro_flow on its own (gro_flow_kernels.hip), shared with UDP receive coalescing:
+// flow_sort_bytes(n) bytes of scratch at an 8-aligned address, split by flow_sort_work. The caller's key pass writes
+// the keys and the identity index to keys[0] / idx[0]; launch_flow_sort (n >= 1) leaves the frame indices in stable
+// ascending key order in d_order. c.rows as above.
+struct FlowSortWork {
+    uint32_t* keys[2];
+    uint32_t* idx[2];
+    uint32_t* table;
+};
+uint64_t flow_sort_bytes(uint64_t n);
+FlowSortWork flow_sort_work(void* work, uint64_t n);
+hipError_t launch_flow_sort(const LaunchCfg& c, uint32_t n, const FlowSortWork& s, uint32_t* d_order, hipStream_t st);
+// UDP receive coalescing (nsx_ugro_*, ugro_kernels.hip): the writable device arrays of include/nsx_csum.h
+// nsx_ugro_out, member for member.
+struct UgroOut {
+    uint64_t* n_super;
+    uint8_t* src;
+    uint8_t* dst;
+    uint16_t* ident;
+    uint8_t* ttl;
+    uint8_t* tclass;
+    uint32_t* flow;
+    uint16_t* src_port;
+    uint16_t* dst_port;
+    uint32_t* gso;
+    uint8_t* data;
+    uint64_t* data_off;
+    uint64_t* first_frame;
+    uint32_t* frame_cnt;
+    uint32_t* frame_seg;
+};
+// Scratch bytes of one launch_ugro / launch_ugro_flow over n frames (whatever the tune; flow >= plain).
+uint64_t ugro_work_bytes(uint64_t n);
+uint64_t ugro_flow_work_bytes(uint64_t n);
+// Datagrams → super-datagrams (ipver 4 / 6); n < 2^32 - 1, work of at least ugro_work_bytes(n). c.run_segs and
+// c.blocks_per_cu as launch_gro.
+hipError_t launch_ugro(const LaunchCfg& c, int ipver, const void* d_base, const uint64_t* d_offsets, uint64_t n,
+                       const uint64_t* valid, const UgroOut& o, void* work, hipStream_t st);
+// Key pass, launch_flow_sort into d_order, then the same passes over that order: one serial chain of launches.
+// n == 0 writes no order. Work of at least ugro_flow_work_bytes(n).
+hipError_t launch_ugro_flow(const LaunchCfg& c, int ipver, const void* d_base, const uint64_t* d_offsets, uint64_t n,
+                            const uint64_t* valid, uint32_t* d_order, const UgroOut& o, void* work, hipStream_t st);
 // The in-place NAT rewrite (nsx_nat_*, nat_kernels.hip): one launch, a lane per frame; none for n == 0. n < 2^32 - 1,
 // slots a power of two <= 2^31, the table 16-byte aligned, ttl_dec <= 255 (nat_api.cpp checks all of it).
 hipError_t launch_nat_rewrite(int ipver, void* d_base, const uint64_t* d_offsets, uint64_t n, const uint64_t* valid,

@@ -186,63 +186,82 @@ uint32_t tile_rows(const LaunchCfg& c) {
     return std::min<uint32_t>((uint32_t)c.rows, kTileRowsMax);
 }
 
-struct FlowWork {
-    uint64_t gro, keys[2], idx[2], table, total;  // byte offsets from the workspace rounded up to 8
+// the sort's own scratch over n keys: byte offsets from an 8-aligned start
+struct SortLayout {
+    uint64_t keys[2], idx[2], table, total;
 };
 
-FlowWork flow_layout(uint64_t n) {
-    FlowWork w;
+SortLayout sort_layout(uint64_t n) {
+    SortLayout w;
     const uint64_t tiles_max = (n + kBlock - 1) / kBlock;  // the smallest tile a tune can ask for
-    w.gro = 0;
-    w.keys[0] = (gro_work_bytes(n) + 7u) & ~7ull;  // launch_gro_ordered's own scratch comes first
+    w.keys[0] = 0;
     w.keys[1] = w.keys[0] + 4 * n;
     w.idx[0] = w.keys[1] + 4 * n;
     w.idx[1] = w.idx[0] + 4 * n;
     w.table = w.idx[1] + 4 * n;
-    w.total = w.table + 4 * (uint64_t)kDigits * tiles_max + 8;  // + the rounding of the caller's pointer
+    w.total = w.table + 4 * (uint64_t)kDigits * tiles_max;
     return w;
 }
 
+// launch_gro_ordered's own scratch comes first, the sort's behind it
+uint64_t flow_sort_at(uint64_t n) { return (gro_work_bytes(n) + 7u) & ~7ull; }
+
 }  // namespace
 
-uint64_t gro_flow_work_bytes(uint64_t n) { return flow_layout(n).total; }
+uint64_t flow_sort_bytes(uint64_t n) { return sort_layout(n).total; }
+
+FlowSortWork flow_sort_work(void* work, uint64_t n) {
+    const SortLayout L = sort_layout(n);
+    uint8_t* w = static_cast<uint8_t*>(work);
+    return {{reinterpret_cast<uint32_t*>(w + L.keys[0]), reinterpret_cast<uint32_t*>(w + L.keys[1])},
+            {reinterpret_cast<uint32_t*>(w + L.idx[0]), reinterpret_cast<uint32_t*>(w + L.idx[1])},
+            reinterpret_cast<uint32_t*>(w + L.table)};
+}
+
+uint64_t gro_flow_work_bytes(uint64_t n) {
+    return flow_sort_at(n) + flow_sort_bytes(n) + 8;  // + the rounding of the caller's pointer
+}
 
 hipError_t launch_gro_flow(const LaunchCfg& c, int ipver, const void* d_base, const uint64_t* d_offsets, uint64_t n64,
                            const uint64_t* valid, uint32_t* d_order, const GroOut& o, void* work, hipStream_t st) {
     const uint32_t n = (uint32_t)n64;  // n < 2^32 - 1 (csum_api.cpp)
-    const FlowWork L = flow_layout(n);
     uint8_t* w = reinterpret_cast<uint8_t*>(((uintptr_t)work + 7u) & ~(uintptr_t)7u);
     if (n) {
-        uint32_t* keys[2] = {reinterpret_cast<uint32_t*>(w + L.keys[0]), reinterpret_cast<uint32_t*>(w + L.keys[1])};
-        uint32_t* idx[2] = {reinterpret_cast<uint32_t*>(w + L.idx[0]), reinterpret_cast<uint32_t*>(w + L.idx[1])};
-        uint32_t* table = reinterpret_cast<uint32_t*>(w + L.table);
+        const FlowSortWork S = flow_sort_work(w + flow_sort_at(n), n);
         const uint8_t* base = static_cast<const uint8_t*>(d_base);
         const uint32_t kgrid = (uint32_t)(((uint64_t)n + kBlock - 1) / kBlock);
         if (ipver == 6)
             hipLaunchKernelGGL(flow_key_kernel<true>, dim3(kgrid), dim3(kBlock), 0, st, base, d_offsets, n, valid,
-                               keys[0], idx[0]);
+                               S.keys[0], S.idx[0]);
         else
             hipLaunchKernelGGL(flow_key_kernel<false>, dim3(kgrid), dim3(kBlock), 0, st, base, d_offsets, n, valid,
-                               keys[0], idx[0]);
-        const uint32_t rows = tile_rows(c), tile_keys = rows * kBlock;
-        const uint32_t ntiles = (uint32_t)(((uint64_t)n + tile_keys - 1) / tile_keys);
-        const uint64_t entries = (uint64_t)kDigits * ntiles;
-        for (uint32_t p = 0; p < kPasses; ++p) {
-            const uint32_t shift = p * kDigitBits, a = p & 1u, b = a ^ 1u;
-            hipLaunchKernelGGL(flow_hist_kernel, dim3(ntiles), dim3(kBlock), 0, st, keys[a], n, tile_keys, shift,
-                               ntiles, table);
-            hipLaunchKernelGGL(flow_scan_kernel, dim3(1), dim3(kBlock), 0, st, table, entries);
-            if (p + 1 < kPasses)
-                hipLaunchKernelGGL(flow_scatter_kernel<false>, dim3(ntiles), dim3(kBlock), 0, st, keys[a], idx[a], n,
-                                   rows, shift, ntiles, table, keys[b], idx[b]);
-            else
-                hipLaunchKernelGGL(flow_scatter_kernel<true>, dim3(ntiles), dim3(kBlock), 0, st, keys[a], idx[a], n,
-                                   rows, shift, ntiles, table, keys[b], d_order);
-        }
-        const hipError_t e = hipGetLastError();
+                               S.keys[0], S.idx[0]);
+        const hipError_t e = launch_flow_sort(c, n, S, d_order, st);
         if (e != hipSuccess) return e;
     }
-    return launch_gro_ordered(c, ipver, d_base, d_offsets, n64, valid, d_order, o, w + L.gro, st);
+    return launch_gro_ordered(c, ipver, d_base, d_offsets, n64, valid, d_order, o, w, st);
+}
+
+// The hist / scan / scatter loop: S.keys[0] / S.idx[0] hold the keys and the identity index of n >= 1 frames.
+// (Defined behind its first caller: the kernels are instantiated, and so laid out in the code object, in the order
+// they always were.)
+hipError_t launch_flow_sort(const LaunchCfg& c, uint32_t n, const FlowSortWork& S, uint32_t* d_order, hipStream_t st) {
+    const uint32_t rows = tile_rows(c), tile_keys = rows * kBlock;
+    const uint32_t ntiles = (uint32_t)(((uint64_t)n + tile_keys - 1) / tile_keys);
+    const uint64_t entries = (uint64_t)kDigits * ntiles;
+    for (uint32_t p = 0; p < kPasses; ++p) {
+        const uint32_t shift = p * kDigitBits, a = p & 1u, b = a ^ 1u;
+        hipLaunchKernelGGL(flow_hist_kernel, dim3(ntiles), dim3(kBlock), 0, st, S.keys[a], n, tile_keys, shift, ntiles,
+                           S.table);
+        hipLaunchKernelGGL(flow_scan_kernel, dim3(1), dim3(kBlock), 0, st, S.table, entries);
+        if (p + 1 < kPasses)
+            hipLaunchKernelGGL(flow_scatter_kernel<false>, dim3(ntiles), dim3(kBlock), 0, st, S.keys[a], S.idx[a], n,
+                               rows, shift, ntiles, S.table, S.keys[b], S.idx[b]);
+        else
+            hipLaunchKernelGGL(flow_scatter_kernel<true>, dim3(ntiles), dim3(kBlock), 0, st, S.keys[a], S.idx[a], n,
+                               rows, shift, ntiles, S.table, S.keys[b], d_order);
+    }
+    return hipGetLastError();
 }
 
 }  // namespace nsx

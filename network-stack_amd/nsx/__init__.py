@@ -155,13 +155,23 @@ def lib() -> ctypes.CDLL:
             "nsx_udp_rx_ipv4_verify_dev_tuned": [vp, vp, u64, vp, vp, vp, vp, vp],
             "nsx_udp_rx_ipv6_verify_dev": [vp, vp, u64, vp, vp, vp],
             "nsx_udp_rx_ipv6_verify_dev_tuned": [vp, vp, u64, vp, vp, vp, vp],
+            "nsx_ugro_work_bytes": [u64, ctypes.POINTER(u64)],
+            "nsx_ugro_flow_work_bytes": [u64, ctypes.POINTER(u64)],
+            "nsx_ugro_ipv4_dev": [vp, vp, u64, vp, vp, vp, u64, vp],
+            "nsx_ugro_ipv6_dev": [vp, vp, u64, vp, vp, vp, u64, vp],
+            "nsx_ugro_ipv4_dev_tuned": [vp, vp, u64, vp, vp, vp, u64, vp, vp],
+            "nsx_ugro_ipv6_dev_tuned": [vp, vp, u64, vp, vp, vp, u64, vp, vp],
+            "nsx_ugro_flow_ipv4_dev": [vp, vp, u64, vp, vp, vp, vp, u64, vp],
+            "nsx_ugro_flow_ipv6_dev": [vp, vp, u64, vp, vp, vp, vp, u64, vp],
+            "nsx_ugro_flow_ipv4_dev_tuned": [vp, vp, u64, vp, vp, vp, vp, u64, vp, vp],
+            "nsx_ugro_flow_ipv6_dev_tuned": [vp, vp, u64, vp, vp, vp, vp, u64, vp, vp],
             "nsx_fixed_launch_count": [u64, u32, u64, vp, ctypes.POINTER(u64)],
             "nsx_ipv4_hdr_launch_count": [vp, u64, u32, u64, vp, ctypes.POINTER(u64)],
         }
         # present since ABI round 6, and the transmit pass since its own change; an older library (same-box A/B against a
         # previous build) lacks them
         optional = {"nsx_stream_release", "nsx_deal_sets_in_use"} | \
-            {k for k in sig if k.startswith(("nsx_tx_", "nsx_tso_", "nsx_gro_", "nsx_nat_", "nsx_udp_"))}
+            {k for k in sig if k.startswith(("nsx_tx_", "nsx_tso_", "nsx_gro_", "nsx_nat_", "nsx_udp_", "nsx_ugro_"))}
         for name, args in sig.items():
             if name in optional and not hasattr(L, name):
                 continue
@@ -1311,6 +1321,105 @@ def udp_rx_ipv6_verify_dev(buf, offsets, mask=None, udp_raw=None, stream=None, t
                                                   _dev_ptr(udp_raw), _stream(stream), _tune(tune)),
            "nsx_udp_rx_ipv6_verify_dev")
     return mask
+
+
+# ---------------------------------------------------------------------------
+# UDP receive coalescing: datagrams in, super-datagrams in UDP segmentation offload's format out (nsx_ugro_*)
+# ---------------------------------------------------------------------------
+# nsx_ugro_out members in order: (name, torch dtype, worst-case element count as a function of (n, alen, buf bytes))
+UGRO_FIELDS = (("n_super", "int64", lambda n, a, b: 1),
+               ("src", "uint8", lambda n, a, b: n * a), ("dst", "uint8", lambda n, a, b: n * a),
+               ("ident", "int16", lambda n, a, b: n), ("ttl", "uint8", lambda n, a, b: n),
+               ("tclass", "uint8", lambda n, a, b: n), ("flow", "int32", lambda n, a, b: n),
+               ("src_port", "int16", lambda n, a, b: n), ("dst_port", "int16", lambda n, a, b: n),
+               ("gso", "int32", lambda n, a, b: n), ("data", "uint8", lambda n, a, b: b),
+               ("data_off", "int64", lambda n, a, b: n + 1), ("first_frame", "int64", lambda n, a, b: n),
+               ("frame_cnt", "int32", lambda n, a, b: n), ("frame_seg", "int32", lambda n, a, b: n))
+
+
+class UgroOut(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name, _, _ in UGRO_FIELDS]
+
+
+def ugro_work_bytes(n: int) -> int:
+    """nsx_ugro_work_bytes: the scratch bytes one ugro_ipv4_dev / ugro_ipv6_dev call over n frames needs."""
+    c = ctypes.c_uint64(0)
+    _check(lib().nsx_ugro_work_bytes(n, ctypes.byref(c)), "nsx_ugro_work_bytes")
+    return c.value
+
+
+def ugro_flow_work_bytes(n: int) -> int:
+    """nsx_ugro_flow_work_bytes: the scratch bytes one ugro_flow_ipv4_dev / ugro_flow_ipv6_dev call over n frames
+    needs (at least ugro_work_bytes(n))."""
+    c = ctypes.c_uint64(0)
+    _check(lib().nsx_ugro_flow_work_bytes(n, ctypes.byref(c)), "nsx_ugro_flow_work_bytes")
+    return c.value
+
+
+def _ugro_dev(ipver: int, buf, offsets, valid, out, work, stream, tune, flow: bool = False, order=None) -> dict:
+    import torch
+    what = f"ugro_flow_ipv{ipver}_dev" if flow else f"ugro_ipv{ipver}_dev"
+    n = _count(offsets, f"{what} offsets")
+    alen = _ip_sizes(ipver)["src"]
+    _span(buf, 0, f"{what} buf", elem=1)
+    _span(valid, 8 * ((n + 63) // 64), f"{what} valid", elem=8)
+    if valid is None:
+        raise ValueError(f"{what}: the UDP receive verify's mask `valid` is required")
+    res = dict(out or {})
+    bad = set(res) - {k for k, _, _ in UGRO_FIELDS}
+    if bad:
+        raise ValueError(f"{what}: unknown output(s) {sorted(bad)}")
+    for k, dt, count in UGRO_FIELDS:
+        need = count(n, alen, buf.numel())
+        if res.get(k) is None:  # worst-case size; never a zero-size tensor, whose address is NULL
+            res[k] = torch.empty(max(need, 1), dtype=getattr(torch, dt), device=offsets.device)
+        size = np.dtype(dt).itemsize
+        _span(res[k], need * size, f"{what} {k}", elem=size)
+    if flow:
+        if order is None:  # never a zero-size tensor, whose address is NULL
+            order = torch.empty(max(n, 1), dtype=torch.int32, device=offsets.device)
+        _span(order, 4 * n, f"{what} order", elem=4)
+    need = ugro_flow_work_bytes(n) if flow else ugro_work_bytes(n)
+    if work is None:
+        work = torch.empty(need, dtype=torch.uint8, device=offsets.device)
+    _span(work, need, f"{what} work")
+    soa = UgroOut(*[_dev_ptr(res[k]) for k, _, _ in UGRO_FIELDS])
+    fn = getattr(lib(), f"nsx_{what}_tuned")
+    args = [_dev_ptr(buf), _dev_ptr(offsets), n, _dev_ptr(valid)] + ([_dev_ptr(order)] if flow else []) + \
+        [ctypes.byref(soa), _dev_ptr(work), work.numel() * work.element_size(), _stream(stream), _tune(tune)]
+    _check(fn(*args), f"nsx_{what}")
+    if flow:
+        res["order"] = order
+    return res
+
+
+def ugro_ipv4_dev(buf, offsets, valid, out=None, work=None, stream=None, tune=None) -> dict:
+    """UDP receive coalescing over packed IPv4/UDP frames: buf / offsets as udp_rx_ipv4_verify_dev, valid = that
+    pass's mask. Returns a dict of device tensors, the members of nsx_ugro_out (UGRO_FIELDS) — n_super (one int64),
+    the per-super-datagram arrays udp_uso_ipv4_build_dev takes, first_frame / frame_cnt, and frame_seg per frame —
+    allocated at worst-case size (n entries, n + 1 offsets, buf.numel() data bytes) unless given in `out`; `work` is
+    scratch of ugro_work_bytes(n) bytes; tune: run_segs = frames per scan block, blocks_per_cu = the copy kernel's
+    grid. Does not synchronise: n_super is in device memory."""
+    return _ugro_dev(4, buf, offsets, valid, out, work, stream, tune)
+
+
+def ugro_ipv6_dev(buf, offsets, valid, out=None, work=None, stream=None, tune=None) -> dict:
+    """The same for IPv6 (src / dst 16 bytes per super-datagram; ident 0; tclass and flow from the header)."""
+    return _ugro_dev(6, buf, offsets, valid, out, work, stream, tune)
+
+
+def ugro_flow_ipv4_dev(buf, offsets, valid, out=None, order=None, work=None, stream=None, tune=None) -> dict:
+    """Flow-keyed UDP receive coalescing (nsx_ugro_flow_ipv4_dev): ugro_ipv4_dev per flow, however the flows
+    interleave in the batch. Returns the UGRO_FIELDS dict plus "order" (n int32: the stable sort of the frame indices
+    by flow key, allocated unless given). first_frame holds positions in `order`, frame_seg stays indexed by the
+    original frame. `work` is scratch of ugro_flow_work_bytes(n) bytes; tune: as ugro_ipv4_dev, and rows = keys per
+    sort tile in units of 256."""
+    return _ugro_dev(4, buf, offsets, valid, out, work, stream, tune, flow=True, order=order)
+
+
+def ugro_flow_ipv6_dev(buf, offsets, valid, out=None, order=None, work=None, stream=None, tune=None) -> dict:
+    """The same for IPv6."""
+    return _ugro_dev(6, buf, offsets, valid, out, work, stream, tune, flow=True, order=order)
 
 
 def fill_splitmix64_dev(buf, seed: int, byte_off: int = 0, stream=None):
