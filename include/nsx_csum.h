@@ -905,6 +905,145 @@ int nsx_nat_ipv6_tcp_rewrite_dev(void* d_base, const uint64_t* d_offsets, uint64
                                  const void* d_table, uint64_t slots, uint32_t ttl_dec, uint64_t* d_hit,
                                  nsx_stream_t stream);
 
+/* IPv4 fragmentation and reassembly (RFC 791 §2.3, §3.2) on device-resident
+ * frames: nsx_frag_ipv4_dev cuts the frames that do not fit their link's MTU
+ * into fragments; nsx_reasm_ipv4_dev puts the fragments of a receive batch back
+ * into whole datagrams, which then go into nsx_rx_ipv4_tcp_verify_dev or
+ * nsx_udp_rx_ipv4_verify_dev (neither of which accepts a fragment). Kernels of
+ * their own (csrc/frag_kernels.hip); no other call changes. IPv4 only: IPv6
+ * fragments in an extension header (RFC 8200 §4.5), and no pass here walks
+ * extension headers.
+ *
+ * Fragmentation. Input as the receive passes take it: n densely packed frames,
+ * frame i = d_base[d_offsets[i], d_offsets[i+1]) of len_i bytes at any
+ * alignment, and d_mtu[i] >= 28, the MTU of the link frame i goes out on. With
+ * per_i = (mtu_i - 20) & ~7, frame i takes cnt_i output slots: 1 if
+ * len_i <= mtu_i, else ceil((len_i - 20) / per_i). The frame map, built as for
+ * segmentation offload: frag_first (n + 1 entries) is the prefix sum of cnt_i;
+ * frag_src (n_frags entries) the source frame of each slot; out_off
+ * (n_frags + 1 entries) is dense, out_off[0] = 0, no padding: the slot of a
+ * frame that fits is len_i bytes, slot j of a frame that does not is
+ * 20 + min(per_i, len_i - 20 - j*per_i) bytes. nsx_frag_count_host writes
+ * frag_first, nsx_frag_layout_host frag_src and out_off; host memory, no GPU.
+ * NSX_EINVAL, with nothing written: a NULL array (h_mtu, and h_frag_src when
+ * there is no slot, may be NULL for n == 0), decreasing offsets, an mtu below
+ * 28, a frame of 2^30 bytes or more, n >= 2^32, an h_frag_first that is not
+ * nsx_frag_count_host's.
+ *
+ * The device rule for frame i; d_status (n entries) receives its status:
+ *   NSX_FRAG_PASS (0)  len_i <= mtu_i: its one slot is the frame byte for byte,
+ *                      whatever it holds.
+ *   NSX_FRAG_CUT (1)   len_i > mtu_i, and the frame is version 4 with IHL 5,
+ *                      its total length equals len_i, DF is clear, and with o
+ *                      its own fragment offset field o*8 + len_i - 20 <= 65535.
+ *   NSX_FRAG_DF (2)    as CUT but DF is set: the caller owes an ICMP
+ *                      "fragmentation needed" (RFC 1191).
+ *   NSX_FRAG_BAD (3)   any other frame longer than its mtu; and any frame
+ *                      whose mtu, as the device sees it, is below 28.
+ * Fragment j of a CUT frame is the frame's 20 header bytes followed by payload
+ * bytes [j*per, min((j+1)*per, len - 20)), with: total length its own; fragment
+ * offset o + j*per/8; MF set on every fragment but the last, which keeps the
+ * frame's own MF (so a fragment can be cut again, as RFC 791 allows: the
+ * offsets add); the reserved and DF bits of byte 6, ident, TOS, TTL, protocol
+ * and the addresses copied; and the header checksum updated from the frame's
+ * own field by RFC 1624 eqn. 3 with the fold defined for nsx_nat_* above, over
+ * word 1 (bytes 2-3) and word 3 (bytes 6-7), both included whether or not they
+ * changed. A valid header stays valid and equals a full recomputation; a wrong
+ * one stays wrong by the same one's-complement difference. For statuses 2 and 3
+ * every byte of the frame's slots is written as zero: a zero version nibble
+ * fails every downstream pass by itself. Nothing outside the slots is written,
+ * and no byte outside a frame's own range is read. A slot whose extent in
+ * d_out_off is not what the rule above gives it (a map that is not the host
+ * helpers') is not written; nor is a frame or slot of 2^30 bytes or more, which
+ * the host helpers refuse: such a frame gets status 3 and its slots stay as
+ * they were.
+ *
+ * nsx_frag_ipv4_dev: NSX_EINVAL for n >= 2^32, n_frags < n, n_frags > 0 with
+ * n == 0, or a NULL pointer with n > 0; n_frags == 0 is then NSX_OK without a
+ * launch (and without looking for a device); then NSX_ENODEV without a GPU.
+ *
+ * Reassembly. Input: d_base, d_offsets (n + 1), n as above. There is no validity
+ * mask: the transport verifies cannot accept a fragment, so this pass checks
+ * the header itself. Frame i of len bytes is a member iff len >= 21; it is
+ * version 4 with IHL 5; its total length equals len; the raw sum over its 20
+ * header bytes is 0xFFFF; it is a fragment: MF is set or its offset field o is
+ * nonzero; and with pay = len - 20: pay >= 1, pay % 8 == 0 when MF is set, and
+ * o*8 + pay <= 65515. is_frag (ceil(n/64) words) holds the member bits; bits
+ * past n are 0.
+ *
+ * Key: FNV-1a as nsx_gro_flow_* defines it, over three little-endian dwords:
+ * header bytes 12-15, header bytes 16-19, and b4 | b5<<8 | b9<<16 (ident and
+ * protocol); a non-member gets 0xFFFFFFFF. Order: let o1 be the stable
+ * ascending argsort of the fragment offset field (0 for a non-member); then
+ * d_order = o1[stable argsort of key[o1]] — two runs of the radix sort of
+ * nsx_gro_flow_*; bit for bit numpy.lexsort((arrival, off, key)). d_order has n
+ * entries and is an output.
+ *
+ * Over the positions p of that order, cont(p) holds iff the frames at p-1 and p
+ * are both members; src, dst, ident and protocol are equal, compared in full (a
+ * key collision costs a datagram and never merges wrongly); MF is set on the
+ * frame at p-1; and o_p*8 == o_{p-1}*8 + pay_{p-1}: exact abutment — an
+ * overlap, a gap or a duplicate breaks the run. A run is a maximal chain of
+ * cont. It is complete iff its first frame has offset 0 and its last has MF
+ * clear; its datagram is then 20 + o_last*8 + pay_last bytes long. Complete
+ * runs are numbered in position order; *n_out (a uint64_t in device memory) is
+ * their count.
+ *
+ * Datagram s is written to out[out_off[s], out_off[s+1]): dense, out_off[0] = 0,
+ * n_out + 1 entries. It is the first fragment's header with the total length
+ * set to the datagram's, MF and the offset cleared (byte 6 & 0xC0 kept, byte 7
+ * zero) and the header checksum recomputed (~sum with the field zero), then each
+ * fragment's payload at out_off[s] + 20 + o*8. first_pos[s] is the position in
+ * d_order of the run's first fragment, frag_cnt[s] the run's length;
+ * frame_seg[i] (n entries, indexed by frame) is the datagram that consumed
+ * frame i, or 0xFFFFFFFF. A member with no datagram is a leftover: the caller
+ * carries it into its next batch. There are no timers and no cross-batch state.
+ * Entries, offsets and bytes past the last one written are left exactly as they
+ * were. Worst-case extents: n entries per array, n + 1 offsets,
+ * d_offsets[n] - d_offsets[0] output bytes.
+ *
+ * RFC 4963: two datagrams with the same (src, dst, ident, protocol) in one
+ * batch are one key here, and their fragments can be mixed into one datagram
+ * whose pieces abut; the transport checksum then refuses it, exactly as on any
+ * RFC 791 host.
+ *
+ * The defining property: for frames with IHL 5, a valid header checksum and DF
+ * clear, nsx_frag_ipv4_dev followed by nsx_reasm_ipv4_dev rebuilds every cut
+ * frame byte for byte, in any order of the fragments; the output with its
+ * out_off goes straight into the receive verifies.
+ *
+ * nsx_reasm_ipv4_dev: NSX_EINVAL before any launch for a NULL pointer or struct
+ * member (d_base and d_order may be NULL when n == 0), n >= 2^32 - 1, or
+ * work_bytes below nsx_reasm_work_bytes(n); then NSX_ENODEV without a GPU.
+ * n == 0 writes *n_out = 0 and out_off[0] = 0 on the stream and no order.
+ * Both calls: no allocation, no host sync, no per-stream counters; each is one
+ * serial chain of launches and can be captured into a graph; 64-bit offsets
+ * throughout: frames may lie past 2^32 in d_base. There are no _host forms. The
+ * _tuned twins are in nsx_frag_tune.h. */
+#define NSX_FRAG_PASS 0
+#define NSX_FRAG_CUT  1
+#define NSX_FRAG_DF   2
+#define NSX_FRAG_BAD  3
+typedef struct {
+    uint64_t* n_out;
+    uint8_t*  out;
+    uint64_t* out_off;
+    uint64_t* first_pos;
+    uint32_t* frag_cnt;
+    uint32_t* frame_seg;    /* per frame */
+    uint64_t* is_frag;      /* ceil(n/64) words */
+} nsx_reasm_out;
+
+int nsx_frag_count_host(const uint64_t* h_offsets, const uint32_t* h_mtu, uint64_t n, uint64_t* h_frag_first);
+int nsx_frag_layout_host(const uint64_t* h_offsets, const uint32_t* h_mtu, const uint64_t* h_frag_first, uint64_t n,
+                         uint32_t* h_frag_src, uint64_t* h_out_off);
+int nsx_frag_ipv4_dev(const void* d_base, const uint64_t* d_offsets, const uint32_t* d_mtu, uint64_t n,
+                      const uint64_t* d_frag_first, const uint32_t* d_frag_src, uint64_t n_frags, uint8_t* d_out,
+                      const uint64_t* d_out_off, uint8_t* d_status, nsx_stream_t stream);
+int nsx_reasm_work_bytes(uint64_t n, uint64_t* out);
+int nsx_reasm_ipv4_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n, uint32_t* d_order,
+                       const nsx_reasm_out* out, void* d_work, uint64_t work_bytes, nsx_stream_t stream);
+
 /* ----------------------------------------------------------------------------
  * Host-resident batches: pinned staging, H2D → kernel → D2H double-buffered
  * over two streams per GPU, segments sharded contiguously across num_gpus

@@ -1,6 +1,6 @@
 // csum_kernels.h — internal launcher interface between the C ABI (csum_api.cpp, nat_api.cpp, udp_api.cpp,
-// ugro_api.cpp, host_batch.cpp) and the gfx950 kernels (csum_kernels.hip, gro_kernels.hip, gro_flow_kernels.hip,
-// nat_kernels.hip, udp_kernels.hip, ugro_kernels.hip). Not a public header.
+// ugro_api.cpp, frag_api.cpp, host_batch.cpp) and the gfx950 kernels (csum_kernels.hip, gro_kernels.hip,
+// gro_flow_kernels.hip, nat_kernels.hip, udp_kernels.hip, ugro_kernels.hip, frag_kernels.hip). Not a public header.
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -196,6 +196,29 @@ hipError_t launch_udp_build(const LaunchCfg& c, int ipver, const IpHdrSoA& ip, c
 // (1..64, default 16), c.blocks_per_cu the grid (default 8). ip_raw (IPv4 only) / udp_raw nullable.
 hipError_t launch_udp_rx(const LaunchCfg& c, int ipver, const void* d_base, const uint64_t* d_offsets, uint64_t n,
                          uint64_t* mask, uint16_t* ip_raw, uint16_t* udp_raw, hipStream_t st);
+// IPv4 fragmentation (nsx_frag_*, frag_kernels.hip): one launch over the n_frags output slots of the frame map, none
+// for n_frags == 0. n < 2^32 (frag_api.cpp). c.blocks_per_cu = the grid (default 8).
+hipError_t launch_frag(const LaunchCfg& c, const void* d_base, const uint64_t* d_offsets, const uint32_t* d_mtu,
+                       uint64_t n, const uint64_t* d_frag_first, const uint32_t* d_frag_src, uint64_t n_frags,
+                       uint8_t* d_out, const uint64_t* d_out_off, uint8_t* d_status, hipStream_t st);
+// IPv4 reassembly (nsx_reasm_*, frag_kernels.hip): the writable device arrays of include/nsx_csum.h nsx_reasm_out,
+// member for member.
+struct ReasmDevOut {
+    uint64_t* n_out;
+    uint8_t* out;
+    uint64_t* out_off;
+    uint64_t* first_pos;
+    uint32_t* frag_cnt;
+    uint32_t* frame_seg;
+    uint64_t* is_frag;
+};
+// Scratch bytes of one launch_reasm over n frames (whatever the tune).
+uint64_t reasm_work_bytes(uint64_t n);
+// Key pass, launch_flow_sort by fragment offset and again by datagram key into d_order, then the run passes and the
+// copy over that order: one serial chain of launches. n < 2^32 - 1; n == 0 writes no order. c.run_segs, c.rows and
+// c.blocks_per_cu as launch_ugro_flow.
+hipError_t launch_reasm(const LaunchCfg& c, const void* d_base, const uint64_t* d_offsets, uint64_t n,
+                        uint32_t* d_order, const ReasmDevOut& out, void* work, hipStream_t st);
 struct TcpParsedSoA {  // device arrays, one entry per segment; every member nullable
     uint16_t* src_port;
     uint16_t* dst_port;

@@ -224,6 +224,41 @@ uint64_t udp_uso_layout(uint32_t iph, const uint64_t* data_off, const uint32_t* 
     return f;
 }
 
+// ---- IPv4 fragmentation's frame map ----
+namespace {
+
+constexpr uint64_t kFragBad = ~0ull;
+constexpr uint64_t kFragLenCap = 1ull << 30;  // a frame this long is refused (include/nsx_csum.h)
+
+// Output slots of a frame of len bytes at this mtu (>= 28): 1 when it fits, else the pieces of (mtu - 20) & ~7 bytes.
+uint64_t frag_slots(uint64_t len, uint32_t mtu) {
+    const uint64_t per = (mtu - 20u) & ~7u;
+    return len <= mtu ? 1 : (len - 20 + per - 1) / per;
+}
+
+// The prefix sum of frag_slots into first (nullable), checked against expect (nullable): the slot count, or kFragBad.
+uint64_t frag_walk(const uint64_t* offsets, const uint32_t* mtu, uint64_t n, const uint64_t* expect, uint64_t* first) {
+    uint64_t f = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (offsets[i + 1] < offsets[i] || offsets[i + 1] - offsets[i] >= kFragLenCap || mtu[i] < 28 ||
+            (expect && expect[i] != f))
+            return kFragBad;
+        f += frag_slots(offsets[i + 1] - offsets[i], mtu[i]);
+    }
+    if (expect && expect[n] != f) return kFragBad;
+    if (first) {  // everything checked before anything is written
+        f = 0;
+        for (uint64_t i = 0; i < n; ++i) {
+            first[i] = f;
+            f += frag_slots(offsets[i + 1] - offsets[i], mtu[i]);
+        }
+        first[n] = f;
+    }
+    return f;
+}
+
+}  // namespace
+
 // ---- the NAT rewrite's translation table ----
 uint32_t nat_hash(const uint8_t* t, uint32_t tuple_bytes) {
     uint32_t h = 0x811C9DC5u;
@@ -321,6 +356,31 @@ int nsx_udp_uso_layout_host(const uint64_t* h_data_off, const uint32_t* h_gso, c
     const uint64_t frames = nsx::tso_walk(nullptr, h_data_off, h_gso, n, h_frame_first, nullptr);
     if (frames == nsx::kTsoBad || (frames && !h_frame_seg)) return NSX_EINVAL;
     nsx::udp_uso_layout(ip_hdr_len, h_data_off, h_gso, n, h_frame_seg, h_out_off);
+    return NSX_OK;
+}
+
+int nsx_frag_count_host(const uint64_t* h_offsets, const uint32_t* h_mtu, uint64_t n, uint64_t* h_frag_first) {
+    if (!h_frag_first || !h_offsets || n >= (1ull << 32) || (n && !h_mtu)) return NSX_EINVAL;
+    return nsx::frag_walk(h_offsets, h_mtu, n, nullptr, h_frag_first) == nsx::kFragBad ? NSX_EINVAL : NSX_OK;
+}
+
+int nsx_frag_layout_host(const uint64_t* h_offsets, const uint32_t* h_mtu, const uint64_t* h_frag_first, uint64_t n,
+                         uint32_t* h_frag_src, uint64_t* h_out_off) {
+    if (!h_out_off || !h_frag_first || !h_offsets || n >= (1ull << 32) || (n && !h_mtu)) return NSX_EINVAL;
+    // everything checked before anything is written: the map must be nsx_frag_count_host's
+    const uint64_t slots = nsx::frag_walk(h_offsets, h_mtu, n, h_frag_first, nullptr);
+    if (slots == nsx::kFragBad || (slots && !h_frag_src)) return NSX_EINVAL;
+    uint64_t f = 0, at = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint64_t len = h_offsets[i + 1] - h_offsets[i], per = (h_mtu[i] - 20u) & ~7u;
+        const uint64_t cnt = nsx::frag_slots(len, h_mtu[i]);
+        for (uint64_t j = 0; j < cnt; ++j, ++f) {
+            h_frag_src[f] = (uint32_t)i;
+            h_out_off[f] = at;
+            at += len <= h_mtu[i] ? len : 20 + std::min(per, len - 20 - j * per);
+        }
+    }
+    h_out_off[f] = at;
     return NSX_OK;
 }
 

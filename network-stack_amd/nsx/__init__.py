@@ -165,13 +165,21 @@ def lib() -> ctypes.CDLL:
             "nsx_ugro_flow_ipv6_dev": [vp, vp, u64, vp, vp, vp, vp, u64, vp],
             "nsx_ugro_flow_ipv4_dev_tuned": [vp, vp, u64, vp, vp, vp, vp, u64, vp, vp],
             "nsx_ugro_flow_ipv6_dev_tuned": [vp, vp, u64, vp, vp, vp, vp, u64, vp, vp],
+            "nsx_frag_count_host": [vp, vp, u64, vp],
+            "nsx_frag_layout_host": [vp, vp, vp, u64, vp, vp],
+            "nsx_frag_ipv4_dev": [vp, vp, vp, u64, vp, vp, u64, vp, vp, vp, vp],
+            "nsx_frag_ipv4_dev_tuned": [vp, vp, vp, u64, vp, vp, u64, vp, vp, vp, vp, vp],
+            "nsx_reasm_work_bytes": [u64, ctypes.POINTER(u64)],
+            "nsx_reasm_ipv4_dev": [vp, vp, u64, vp, vp, vp, u64, vp],
+            "nsx_reasm_ipv4_dev_tuned": [vp, vp, u64, vp, vp, vp, u64, vp, vp],
             "nsx_fixed_launch_count": [u64, u32, u64, vp, ctypes.POINTER(u64)],
             "nsx_ipv4_hdr_launch_count": [vp, u64, u32, u64, vp, ctypes.POINTER(u64)],
         }
         # present since ABI round 6, and the transmit pass since its own change; an older library (same-box A/B against a
         # previous build) lacks them
         optional = {"nsx_stream_release", "nsx_deal_sets_in_use"} | \
-            {k for k in sig if k.startswith(("nsx_tx_", "nsx_tso_", "nsx_gro_", "nsx_nat_", "nsx_udp_", "nsx_ugro_"))}
+            {k for k in sig if k.startswith(("nsx_tx_", "nsx_tso_", "nsx_gro_", "nsx_nat_", "nsx_udp_", "nsx_ugro_", "nsx_frag_",
+                                           "nsx_reasm_"))}
         for name, args in sig.items():
             if name in optional and not hasattr(L, name):
                 continue
@@ -1420,6 +1428,126 @@ def ugro_flow_ipv4_dev(buf, offsets, valid, out=None, order=None, work=None, str
 def ugro_flow_ipv6_dev(buf, offsets, valid, out=None, order=None, work=None, stream=None, tune=None) -> dict:
     """The same for IPv6."""
     return _ugro_dev(6, buf, offsets, valid, out, work, stream, tune, flow=True, order=order)
+
+
+# ---------------------------------------------------------------------------
+# IPv4 fragmentation and reassembly (nsx_frag_*, nsx_reasm_*)
+# ---------------------------------------------------------------------------
+FRAG_PASS, FRAG_CUT, FRAG_DF, FRAG_BAD = 0, 1, 2, 3
+# nsx_reasm_out members in order: (name, torch dtype, worst-case element count as a function of (n, buf bytes))
+REASM_FIELDS = (("n_out", "int64", lambda n, b: 1), ("out", "uint8", lambda n, b: b),
+                ("out_off", "int64", lambda n, b: n + 1), ("first_pos", "int64", lambda n, b: n),
+                ("frag_cnt", "int32", lambda n, b: n), ("frame_seg", "int32", lambda n, b: n),
+                ("is_frag", "int64", lambda n, b: (n + 63) // 64))
+
+
+class ReasmOut(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name, _, _ in REASM_FIELDS]
+
+
+def _frag_host_args(offsets, mtu, what: str):
+    offsets = np.ascontiguousarray(offsets, np.uint64)
+    mtu = np.ascontiguousarray(mtu, np.uint32)
+    n = offsets.size - 1
+    if n < 0 or mtu.size < n:
+        raise ValueError(f"{what}: offsets needs n + 1 entries and mtu n, got {offsets.size} and {mtu.size}")
+    return offsets, mtu, n
+
+
+def frag_count_host(offsets: np.ndarray, mtu: np.ndarray) -> np.ndarray:
+    """nsx_frag_count_host: frag_first (n + 1), the prefix sum of the output slots each frame takes at its mtu."""
+    offsets, mtu, n = _frag_host_args(offsets, mtu, "frag_count_host")
+    first = np.zeros(n + 1, np.uint64)
+    _check(lib().nsx_frag_count_host(_np_ptr(offsets), _np_ptr(mtu), n, _np_ptr(first)), "nsx_frag_count_host")
+    return first
+
+
+def frag_layout_host(offsets: np.ndarray, mtu: np.ndarray, frag_first: np.ndarray):
+    """nsx_frag_layout_host: (frag_src[n_frags], out_off[n_frags + 1]) over frag_count_host's map; dense slots."""
+    offsets, mtu, n = _frag_host_args(offsets, mtu, "frag_layout_host")
+    first = np.ascontiguousarray(frag_first, np.uint64)
+    if first.size < n + 1:
+        raise ValueError(f"frag_layout_host frag_first: {first.size} entries for {n} frames")
+    # the C call checks frag_first against its own count before it writes: these sizes hold whenever it writes
+    nf = int(first[n])
+    if nf >= 1 << 40:
+        raise ValueError(f"frag_layout_host frag_first: {nf} slots")
+    src = np.zeros(max(nf, 1), np.uint32)
+    out = np.zeros(nf + 1, np.uint64)
+    _check(lib().nsx_frag_layout_host(_np_ptr(offsets), _np_ptr(mtu), _np_ptr(first), n, _np_ptr(src), _np_ptr(out)),
+           "nsx_frag_layout_host")
+    return src[:nf], out
+
+
+def frag_ipv4_dev(buf, offsets, mtu, frag_first, frag_src, out, out_off, status=None, stream=None, tune=None,
+                  n_frags=None):
+    """IPv4 fragmentation over packed frames: buf / offsets as the receive passes take them, mtu (uint32 per frame),
+    and the frame map of frag_count_host / frag_layout_host as device tensors (n_frags defaults to out_off's length
+    less one). Writes the slots to out + out_off[t] and returns status (uint8 per frame: FRAG_PASS, FRAG_CUT, FRAG_DF,
+    FRAG_BAD; allocated unless given). The slot extents are in device memory: `out` must hold out_off[n_frags] bytes.
+    tune: blocks_per_cu = the grid."""
+    import torch
+    what = "frag_ipv4_dev"
+    n = _count(offsets, f"{what} offsets")
+    nf = _count(out_off, f"{what} out_off") if n_frags is None else int(n_frags)
+    if nf < n or (n == 0 and nf):
+        raise ValueError(f"{what}: {nf} slots for {n} frames")
+    if status is None:  # never a zero-size tensor, whose address is NULL
+        status = torch.empty(max(n, 1), dtype=torch.uint8, device=offsets.device)
+    _span(buf, 0, f"{what} buf", elem=1)
+    _span(mtu, 4 * n, f"{what} mtu", elem=4)
+    _span(frag_first, 8 * (n + 1), f"{what} frag_first", elem=8)
+    _span(frag_src, 4 * nf, f"{what} frag_src", elem=4)
+    _span(out_off, 8 * (nf + 1), f"{what} out_off", elem=8)
+    _span(out, 0, f"{what} out", elem=1)
+    _span(status, n, f"{what} status", elem=1)
+    _check(lib().nsx_frag_ipv4_dev_tuned(_dev_ptr(buf), _dev_ptr(offsets), _dev_ptr(mtu), n, _dev_ptr(frag_first),
+                                         _dev_ptr(frag_src), nf, _dev_ptr(out), _dev_ptr(out_off), _dev_ptr(status),
+                                         _stream(stream), _tune(tune)), f"nsx_{what}")
+    return status
+
+
+def reasm_work_bytes(n: int) -> int:
+    """nsx_reasm_work_bytes: the scratch bytes one reasm_ipv4_dev call over n frames needs."""
+    c = ctypes.c_uint64(0)
+    _check(lib().nsx_reasm_work_bytes(n, ctypes.byref(c)), "nsx_reasm_work_bytes")
+    return c.value
+
+
+def reasm_ipv4_dev(buf, offsets, out=None, order=None, work=None, stream=None, tune=None) -> dict:
+    """IPv4 reassembly over packed frames: returns a dict of device tensors, the members of nsx_reasm_out
+    (REASM_FIELDS) — n_out (one int64), the datagrams in out / out_off, first_pos / frag_cnt per datagram, frame_seg
+    per frame, the member bitmask is_frag — allocated at worst-case size (n entries, n + 1 offsets, buf.numel() output
+    bytes) unless given in `out`, plus "order" (n int32, allocated unless given). `work` is scratch of
+    reasm_work_bytes(n) bytes; tune: run_segs = frames per scan block, blocks_per_cu = the copy kernel's grid, rows =
+    keys per sort tile in units of 256. Does not synchronise: n_out is in device memory."""
+    import torch
+    what = "reasm_ipv4_dev"
+    n = _count(offsets, f"{what} offsets")
+    _span(buf, 0, f"{what} buf", elem=1)
+    res = dict(out or {})
+    bad = set(res) - {k for k, _, _ in REASM_FIELDS}
+    if bad:
+        raise ValueError(f"{what}: unknown output(s) {sorted(bad)}")
+    for k, dt, count in REASM_FIELDS:
+        need = count(n, buf.numel())
+        if res.get(k) is None:  # worst-case size; never a zero-size tensor, whose address is NULL
+            res[k] = torch.empty(max(need, 1), dtype=getattr(torch, dt), device=offsets.device)
+        size = np.dtype(dt).itemsize
+        _span(res[k], need * size, f"{what} {k}", elem=size)
+    if order is None:  # never a zero-size tensor, whose address is NULL
+        order = torch.empty(max(n, 1), dtype=torch.int32, device=offsets.device)
+    _span(order, 4 * n, f"{what} order", elem=4)
+    need = reasm_work_bytes(n)
+    if work is None:
+        work = torch.empty(need, dtype=torch.uint8, device=offsets.device)
+    _span(work, need, f"{what} work")
+    soa = ReasmOut(*[_dev_ptr(res[k]) for k, _, _ in REASM_FIELDS])
+    _check(lib().nsx_reasm_ipv4_dev_tuned(_dev_ptr(buf), _dev_ptr(offsets), n, _dev_ptr(order), ctypes.byref(soa),
+                                          _dev_ptr(work), work.numel() * work.element_size(), _stream(stream),
+                                          _tune(tune)), f"nsx_{what}")
+    res["order"] = order
+    return res
 
 
 def fill_splitmix64_dev(buf, seed: int, byte_off: int = 0, stream=None):
