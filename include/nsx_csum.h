@@ -1044,6 +1044,185 @@ int nsx_reasm_work_bytes(uint64_t n, uint64_t* out);
 int nsx_reasm_ipv4_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n, uint32_t* d_order,
                        const nsx_reasm_out* out, void* d_work, uint64_t work_bytes, nsx_stream_t stream);
 
+/* ICMP and ICMPv6 (RFC 792, RFC 4443) on device-resident frames: error
+ * generation for the frames the other passes hand back (NSX_FRAG_DF: RFC 1191
+ * "fragmentation needed"; the frames the NAT rewrite refuses on TTL: "time
+ * exceeded"), a receive verify that tells a ping from garbage, and the echo
+ * reply written over the request in place. Kernels of their own
+ * (csrc/icmp_kernels.hip); no other call changes. Input everywhere as the
+ * receive passes take it: n densely packed frames, frame i = d_base[d_offsets[i],
+ * d_offsets[i+1]) of len_i bytes at any alignment, d_offsets with n + 1 entries.
+ *
+ * Error generation (nsx_icmp_err_ipv4_dev / nsx_icmp_err_ipv6_dev). d_req holds
+ * one request word per frame: 0 is no request, else bits 0-7 are the ICMP type,
+ * bits 8-15 the code and bits 16-31 must be 0. Allowed types: 3 (destination
+ * unreachable), 11 (time exceeded) and 12 (parameter problem) on IPv4; 1
+ * (destination unreachable), 2 (packet too big), 3 (time exceeded) and 4
+ * (parameter problem) on IPv6; any code. d_arg[i] (d_arg NULL: all zero) is
+ * written big-endian into ICMP header bytes 4-7: the next-hop MTU in its low
+ * half on IPv4 (RFC 1191), the 32-bit MTU on IPv6, the pointer (ptr << 24 on
+ * IPv4, RFC 792; the 32-bit pointer on IPv6). cfg is host memory read at call
+ * time: src our own address (IPv4: its first 4 bytes), ttl the TTL / hop limit
+ * of every message (ttl > 255 is NSX_EINVAL), ident0 the first IPv4 ident,
+ * max_out the most messages one call makes.
+ *
+ * status (n entries) receives, by the first rule that matches:
+ *   NSX_ICMP_NONE (0)     the request is 0. The frame is not read.
+ *   NSX_ICMP_BAD (3)      the request is not an allowed one (the frame is then
+ *                         not read either), or the frame is malformed. IPv4:
+ *                         fewer than 20 bytes, version != 4, IHL < 5, IHL*4 >
+ *                         len, or total length != len. IPv6: fewer than 40
+ *                         bytes, version != 6, or 40 + payload length != len.
+ *   NSX_ICMP_QUIET (2)    the RFCs say to stay silent. IPv4 (RFC 1122 §3.2.2,
+ *                         RFC 1812 §4.3.2.7): the fragment offset field is
+ *                         nonzero (MF alone does not count: the first fragment
+ *                         is answered); src is 0.0.0.0 or src[0] >= 224;
+ *                         dst[0] >= 224; the protocol is 1 and the ICMP type
+ *                         byte at frame byte IHL*4 is absent or is not one of
+ *                         the query types 0, 8, 9, 10, 13, 14, 15, 16, 17, 18.
+ *                         IPv6 (RFC 4443 §2.4(e)): src is :: or src[0] == 0xFF;
+ *                         dst[0] == 0xFF, unless the request is type 2, or type
+ *                         4 with code 2; Next Header is 58 and the type byte at
+ *                         frame byte 40 is absent, is below 128 (an error), or
+ *                         is 137 (a redirect). Extension headers are not
+ *                         walked: an ICMPv6 error behind one is answered.
+ *   NSX_ICMP_LIMITED (4)  the frame's rank among the frames not refused above,
+ *                         in frame order, is >= max_out: the per-call rate cap
+ *                         of RFC 1812 §4.3.2.8 and RFC 4443 §2.4(f).
+ *   NSX_ICMP_SENT (1)     everything else.
+ * The SENT frames are numbered in frame order, s = 0 .. n_out - 1; *n_out is a
+ * uint64_t in device memory; src_frame[s] is the frame's index; out_off is
+ * dense, n_out + 1 entries, out_off[0] = 0. Message s is hdr + 8 + q bytes at
+ * out[out_off[s], out_off[s+1]), q = min(len, Q): Q = 548 on IPv4 (RFC 1812
+ * §4.3.2.3: 576 bytes in all), 1232 on IPv6 (RFC 4443 §2.4(c): 1280 in all).
+ *   IPv4: 45 C0, the total length 28 + q, ident = (ident0 + s) mod 2^16, 00 00,
+ *         cfg.ttl, 01, the header checksum (~sum with the field zero); src =
+ *         cfg.src, dst = the offending frame's src; type, code, the ICMP
+ *         checksum — ~raw over the 8 + q ICMP bytes with the field zero, an odd
+ *         tail padded with a zero byte (ICMP has no 0 -> 0xFFFF rule) — d_arg
+ *         big-endian; then the frame's first q bytes.
+ *   IPv6: 60 00 00 00, the payload length 8 + q, 3A, cfg.ttl; cfg.src, the
+ *         offending frame's src; type, code, the checksum — ~raw over the
+ *         RFC 8200 §8.1 pseudo-header (src, dst, the 32-bit upper-layer length
+ *         8 + q, next header 58) ‖ the message — d_arg big-endian; the quote.
+ * Entries, offsets and bytes past the last one written stay as they were; n == 0
+ * writes *n_out = 0 and out_off[0] = 0 on the stream. Worst-case extents:
+ * min(n, max_out) entries of src_frame, one more of out_off, and SUM_i (hdr + 8
+ * + min(len_i, Q)) output bytes (at most min(n, max_out) * (hdr + 8 + Q)); the
+ * cap bounds them. d_work is scratch of nsx_icmp_err_work_bytes(n) bytes
+ * (nondecreasing in n), work_bytes what the caller really has.
+ *
+ * Request helpers, so that frag -> errors and NAT -> errors stay on the device.
+ * Each is one launch, writes d_req[i] and d_arg[i] only where its condition
+ * holds and leaves every other entry as it was: the caller zeroes the arrays
+ * first, and the helpers compose on the same arrays.
+ *   nsx_icmp_req_frag_dev       d_status[i] == NSX_FRAG_DF (nsx_frag_ipv4_dev's
+ *                               status): req = 3 | 4<<8, arg = d_mtu[i] & 0xFFFF.
+ *   nsx_icmp_req_ttl_ipv4_dev,  frame i's d_valid bit is set, the frame holds a
+ *   nsx_icmp_req_ttl_ipv6_dev   whole IP header of its version (IPv4: 20 bytes
+ *                               or more, version 4, 5 <= IHL, IHL*4 <= len;
+ *                               IPv6: 40 bytes or more, version 6 — re-checked,
+ *                               so a wrong mask reads nothing outside the frame
+ *                               and a clear bit reads nothing at all) and its
+ *                               TTL / hop limit t satisfies t <= ttl_dec: req =
+ *                               11 (IPv6: 3), code 0, arg = 0. With the receive
+ *                               pass's mask this is exactly the set the NAT
+ *                               rewrite refuses on TTL. ttl_dec > 255 is
+ *                               NSX_EINVAL.
+ *
+ * Receive verify (nsx_icmp_rx_ipv4_verify_dev / nsx_icmp_rx_ipv6_verify_dev),
+ * in the shape of nsx_udp_rx_*_verify_dev. Frame i is well-formed iff
+ *   IPv4: version 4, IHL >= 5, IHL*4 + 8 <= len, total length == len, MF clear
+ *         and fragment offset 0, protocol 1;
+ *   IPv6: len >= 48, version 6, 40 + payload length == len, Next Header 58
+ *         (extension headers are not walked).
+ * Bit (i % 64) of d_mask[i / 64] is set iff frame i is well-formed and verifies:
+ * IPv4, the raw sum over the IHL*4 header bytes is 0xFFFF and the raw sum over
+ * bytes [IHL*4, len) is 0xFFFF (ICMP has no pseudo-header); IPv6, the raw sum
+ * over the RFC 8200 §8.1 pseudo-header (the frame's own addresses, len - 40,
+ * 58) ‖ bytes [40, len) is 0xFFFF. There is no zero-checksum exception on
+ * either. d_ip_raw (IPv4, nullable) is the header's raw sum, 0 when the frame
+ * holds fewer than 20 bytes, IHL < 5 or IHL*4 exceeds the frame; d_icmp_raw
+ * (nullable) is that raw, 0 unless the frame is well-formed; d_type (nullable, n
+ * uint16_t) is type << 8 | code, and 0xFFFF unless the bit is set: the demux a
+ * caller needs to pick the echo requests. Bits past n in the last word are 0;
+ * d_mask holds ceil(n/64) words. The split over the waves is static.
+ *
+ * Echo reply in place (nsx_icmp_echo_reply_ipv4_dev / _ipv6_dev). Frame i is
+ * answered iff its d_valid bit is set (d_valid: the verify's mask, required);
+ * it is well-formed as the verify defines (re-checked here, as the NAT rewrite
+ * does, so a wrong mask never makes the kernel touch a byte outside the frame's
+ * own range, nor a frame whose bit is clear at all; the sums are not looked
+ * at); it is type 8 code 0 (IPv6: type 128 code 0); and dst[0] < 224 (IPv6:
+ * dst[0] != 0xFF), because the old dst becomes the new src. An answered frame
+ * changes only in: src and dst, which are swapped; TTL / hop limit, which
+ * becomes ttl (ttl > 255 is NSX_EINVAL); the type, which becomes 0 (IPv6: 129);
+ * the IPv4 header checksum, updated by RFC 1624 eqn. 3 with the fold defined for
+ * nsx_nat_* above over the word at bytes 8-9; and the ICMP checksum, updated
+ * the same way over ICMP word 0. The address swap leaves both the header sum
+ * and the IPv6 pseudo-header sum unchanged, and the hop limit is covered by no
+ * checksum. IP options and the payload are neither read nor written. A frame
+ * that is not answered is left byte for byte as it was. Bit (i % 64) of
+ * d_hit[i / 64] is set iff frame i was answered; bits past n are 0; d_hit has
+ * ceil(n/64) words and is required. Consequence: a verified request becomes a
+ * reply that verifies and equals a full recomputation (~sum with the field
+ * zero), bit for bit; a wrong one stays wrong by the same one's-complement
+ * difference.
+ *
+ * All calls: NSX_EINVAL before anything else — a NULL pointer (every array may
+ * be NULL when n == 0, except cfg, the out struct, its n_out and out_off, and
+ * d_work of the error calls; d_arg of the error calls and the nullable outputs
+ * of the verify may always be NULL), n >= 2^32 - 1, ttl or ttl_dec > 255,
+ * work_bytes below nsx_icmp_err_work_bytes(n) — then NSX_ENODEV without a GPU;
+ * n == 0 is then NSX_OK without a launch (the error calls: with the one that
+ * writes *n_out and out_off[0]). No allocation, no host sync, no per-stream
+ * counters: each call is one serial chain of launches and can be captured into
+ * a graph; 64-bit offsets throughout: frames may lie past 2^32 in d_base. No
+ * byte outside a frame's own range is read, and no byte outside a slot or frame
+ * that the rules name is written. There are no _host forms and no multi-GPU
+ * sharding. The _tuned twins of the error and verify calls are in
+ * nsx_icmp_tune.h. */
+#define NSX_ICMP_NONE    0
+#define NSX_ICMP_SENT    1
+#define NSX_ICMP_QUIET   2
+#define NSX_ICMP_BAD     3
+#define NSX_ICMP_LIMITED 4
+typedef struct {
+    uint8_t  src[16];       /* our own address; IPv4: the first 4 bytes */
+    uint32_t ttl;           /* TTL / hop limit of every message, <= 255 */
+    uint32_t ident0;        /* IPv4: message s carries (ident0 + s) mod 2^16 */
+    uint64_t max_out;       /* the most messages one call makes */
+} nsx_icmp_err_cfg;         /* host memory, read at call time */
+typedef struct {
+    uint64_t* n_out;
+    uint8_t*  out;
+    uint64_t* out_off;
+    uint32_t* src_frame;
+    uint8_t*  status;       /* per frame */
+} nsx_icmp_err_out;         /* device arrays */
+
+int nsx_icmp_err_work_bytes(uint64_t n, uint64_t* out);
+int nsx_icmp_err_ipv4_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n, const uint32_t* d_req,
+                          const uint32_t* d_arg, const nsx_icmp_err_cfg* cfg, const nsx_icmp_err_out* out,
+                          void* d_work, uint64_t work_bytes, nsx_stream_t stream);
+int nsx_icmp_err_ipv6_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n, const uint32_t* d_req,
+                          const uint32_t* d_arg, const nsx_icmp_err_cfg* cfg, const nsx_icmp_err_out* out,
+                          void* d_work, uint64_t work_bytes, nsx_stream_t stream);
+int nsx_icmp_req_frag_dev(const uint8_t* d_status, const uint32_t* d_mtu, uint64_t n, uint32_t* d_req, uint32_t* d_arg,
+                          nsx_stream_t stream);
+int nsx_icmp_req_ttl_ipv4_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n, const uint64_t* d_valid,
+                              uint32_t ttl_dec, uint32_t* d_req, uint32_t* d_arg, nsx_stream_t stream);
+int nsx_icmp_req_ttl_ipv6_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n, const uint64_t* d_valid,
+                              uint32_t ttl_dec, uint32_t* d_req, uint32_t* d_arg, nsx_stream_t stream);
+int nsx_icmp_rx_ipv4_verify_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n, uint64_t* d_mask,
+                                uint16_t* d_ip_raw, uint16_t* d_icmp_raw, uint16_t* d_type, nsx_stream_t stream);
+int nsx_icmp_rx_ipv6_verify_dev(const void* d_base, const uint64_t* d_offsets, uint64_t n, uint64_t* d_mask,
+                                uint16_t* d_icmp_raw, uint16_t* d_type, nsx_stream_t stream);
+int nsx_icmp_echo_reply_ipv4_dev(void* d_base, const uint64_t* d_offsets, uint64_t n, const uint64_t* d_valid,
+                                 uint32_t ttl, uint64_t* d_hit, nsx_stream_t stream);
+int nsx_icmp_echo_reply_ipv6_dev(void* d_base, const uint64_t* d_offsets, uint64_t n, const uint64_t* d_valid,
+                                 uint32_t ttl, uint64_t* d_hit, nsx_stream_t stream);
+
 /* ----------------------------------------------------------------------------
  * Host-resident batches: pinned staging, H2D → kernel → D2H double-buffered
  * over two streams per GPU, segments sharded contiguously across num_gpus

@@ -172,6 +172,20 @@ def lib() -> ctypes.CDLL:
             "nsx_reasm_work_bytes": [u64, ctypes.POINTER(u64)],
             "nsx_reasm_ipv4_dev": [vp, vp, u64, vp, vp, vp, u64, vp],
             "nsx_reasm_ipv4_dev_tuned": [vp, vp, u64, vp, vp, vp, u64, vp, vp],
+            "nsx_icmp_err_work_bytes": [u64, ctypes.POINTER(u64)],
+            "nsx_icmp_err_ipv4_dev": [vp, vp, u64, vp, vp, vp, vp, vp, u64, vp],
+            "nsx_icmp_err_ipv6_dev": [vp, vp, u64, vp, vp, vp, vp, vp, u64, vp],
+            "nsx_icmp_err_ipv4_dev_tuned": [vp, vp, u64, vp, vp, vp, vp, vp, u64, vp, vp],
+            "nsx_icmp_err_ipv6_dev_tuned": [vp, vp, u64, vp, vp, vp, vp, vp, u64, vp, vp],
+            "nsx_icmp_req_frag_dev": [vp, vp, u64, vp, vp, vp],
+            "nsx_icmp_req_ttl_ipv4_dev": [vp, vp, u64, vp, u32, vp, vp, vp],
+            "nsx_icmp_req_ttl_ipv6_dev": [vp, vp, u64, vp, u32, vp, vp, vp],
+            "nsx_icmp_rx_ipv4_verify_dev": [vp, vp, u64, vp, vp, vp, vp, vp],
+            "nsx_icmp_rx_ipv4_verify_dev_tuned": [vp, vp, u64, vp, vp, vp, vp, vp, vp],
+            "nsx_icmp_rx_ipv6_verify_dev": [vp, vp, u64, vp, vp, vp, vp],
+            "nsx_icmp_rx_ipv6_verify_dev_tuned": [vp, vp, u64, vp, vp, vp, vp, vp],
+            "nsx_icmp_echo_reply_ipv4_dev": [vp, vp, u64, vp, u32, vp, vp],
+            "nsx_icmp_echo_reply_ipv6_dev": [vp, vp, u64, vp, u32, vp, vp],
             "nsx_fixed_launch_count": [u64, u32, u64, vp, ctypes.POINTER(u64)],
             "nsx_ipv4_hdr_launch_count": [vp, u64, u32, u64, vp, ctypes.POINTER(u64)],
         }
@@ -179,7 +193,7 @@ def lib() -> ctypes.CDLL:
         # previous build) lacks them
         optional = {"nsx_stream_release", "nsx_deal_sets_in_use"} | \
             {k for k in sig if k.startswith(("nsx_tx_", "nsx_tso_", "nsx_gro_", "nsx_nat_", "nsx_udp_", "nsx_ugro_", "nsx_frag_",
-                                           "nsx_reasm_"))}
+                                           "nsx_reasm_", "nsx_icmp_"))}
         for name, args in sig.items():
             if name in optional and not hasattr(L, name):
                 continue
@@ -1548,6 +1562,206 @@ def reasm_ipv4_dev(buf, offsets, out=None, order=None, work=None, stream=None, t
                                           _tune(tune)), f"nsx_{what}")
     res["order"] = order
     return res
+
+
+# ---------------------------------------------------------------------------
+# ICMP: error generation, request helpers, receive verify and the in-place echo reply (nsx_icmp_*)
+# ---------------------------------------------------------------------------
+ICMP_NONE, ICMP_SENT, ICMP_QUIET, ICMP_BAD, ICMP_LIMITED = 0, 1, 2, 3, 4
+ICMP_HDR = {4: 28, 6: 48}       # IP header + ICMP header of a generated message
+ICMP_QUOTE = {4: 548, 6: 1232}  # the most bytes of the offending frame a message quotes
+# nsx_icmp_err_out members in order: (name, torch dtype, worst-case element count as a function of (n, m, out bytes)),
+# m = min(n, max_out) the most messages
+ICMP_ERR_FIELDS = (("n_out", "int64", lambda n, m, b: 1), ("out", "uint8", lambda n, m, b: b),
+                   ("out_off", "int64", lambda n, m, b: m + 1), ("src_frame", "int32", lambda n, m, b: m),
+                   ("status", "uint8", lambda n, m, b: n))
+
+
+class IcmpErrCfg(ctypes.Structure):
+    _fields_ = [("src", ctypes.c_uint8 * 16), ("ttl", ctypes.c_uint32), ("ident0", ctypes.c_uint32),
+                ("max_out", ctypes.c_uint64)]
+
+
+class IcmpErrOut(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name, _, _ in ICMP_ERR_FIELDS]
+
+
+def icmp_err_work_bytes(n: int) -> int:
+    """nsx_icmp_err_work_bytes: the scratch bytes one icmp_err_ipv4_dev / icmp_err_ipv6_dev call over n frames needs."""
+    c = ctypes.c_uint64(0)
+    _check(lib().nsx_icmp_err_work_bytes(n, ctypes.byref(c)), "nsx_icmp_err_work_bytes")
+    return c.value
+
+
+def icmp_err_out_bytes(ipver: int, n: int, max_out: int, buf_bytes: int) -> int:
+    """The worst-case bytes of `out`: min(n, max_out) messages of a full quote each, and never more than the batch's
+    own bytes plus a header per message."""
+    m = min(n, max_out)
+    return min(m * (ICMP_HDR[ipver] + ICMP_QUOTE[ipver]), buf_bytes + m * ICMP_HDR[ipver])
+
+
+def _icmp_err_dev(ipver: int, buf, offsets, req, arg, src, ttl, ident0, max_out, out, work, stream, tune) -> dict:
+    import torch
+    what = f"icmp_err_ipv{ipver}_dev"
+    n = _count(offsets, f"{what} offsets")
+    max_out = n if max_out is None else int(max_out)
+    src = bytes(src)
+    if len(src) != (4 if ipver == 4 else 16):
+        raise ValueError(f"{what}: src must be {4 if ipver == 4 else 16} address bytes, got {len(src)}")
+    if not 0 <= ttl < 1 << 32 or not 0 <= ident0 < 1 << 32 or not 0 <= max_out < 1 << 64:
+        raise ValueError(f"{what}: ttl, ident0 and max_out must be unsigned, got {ttl}, {ident0}, {max_out}")
+    _span(buf, 0, f"{what} buf", elem=1)
+    if req is None:
+        raise ValueError(f"{what}: the request words `req` are required")
+    _span(req, 4 * n, f"{what} req", elem=4)
+    _span(arg, 4 * n, f"{what} arg", elem=4)
+    res = dict(out or {})
+    bad = set(res) - {k for k, _, _ in ICMP_ERR_FIELDS}
+    if bad:
+        raise ValueError(f"{what}: unknown output(s) {sorted(bad)}")
+    m = min(n, max_out)
+    ob = icmp_err_out_bytes(ipver, n, max_out, buf.numel())
+    for k, dt, count in ICMP_ERR_FIELDS:
+        need = count(n, m, ob)
+        if res.get(k) is None:  # worst-case size; never a zero-size tensor, whose address is NULL
+            res[k] = torch.empty(max(need, 1), dtype=getattr(torch, dt), device=offsets.device)
+        size = np.dtype(dt).itemsize
+        # the bytes of `out` are data-dependent (out_off is in device memory): a caller's own tensor is taken as given
+        _span(res[k], 0 if k == "out" and out and out.get("out") is not None else need * size, f"{what} {k}", elem=size)
+    need = icmp_err_work_bytes(n)
+    if work is None:
+        work = torch.empty(need, dtype=torch.uint8, device=offsets.device)
+    _span(work, need, f"{what} work")
+    cfg = IcmpErrCfg((ctypes.c_uint8 * 16)(*src), ttl, ident0, max_out)
+    soa = IcmpErrOut(*[_dev_ptr(res[k]) for k, _, _ in ICMP_ERR_FIELDS])
+    fn = getattr(lib(), f"nsx_{what}_tuned")
+    _check(fn(_dev_ptr(buf), _dev_ptr(offsets), n, _dev_ptr(req), _dev_ptr(arg), ctypes.byref(cfg), ctypes.byref(soa),
+              _dev_ptr(work), work.numel() * work.element_size(), _stream(stream), _tune(tune)), f"nsx_{what}")
+    return res
+
+
+def icmp_err_ipv4_dev(buf, offsets, req, src, arg=None, ttl: int = 64, ident0: int = 0, max_out: int | None = None,
+                      out=None, work=None, stream=None, tune=None) -> dict:
+    """ICMP error generation over packed IPv4 frames (nsx_icmp_err_ipv4_dev): buf / offsets as the receive passes take
+    them, req one request word per frame (0 none, else type | code << 8; int32), arg the word for ICMP header bytes
+    4-7 (None: all zero), src our own 4 address bytes, max_out the most messages (default n). Returns a dict of device
+    tensors, the members of nsx_icmp_err_out (ICMP_ERR_FIELDS) — n_out (one int64), the messages in out / out_off,
+    src_frame per message, status per frame (ICMP_NONE, ICMP_SENT, ICMP_QUIET, ICMP_BAD, ICMP_LIMITED) — allocated at
+    worst-case size (icmp_err_out_bytes) unless given in `out`. `work` is scratch of icmp_err_work_bytes(n) bytes;
+    tune: run_segs = frames per scan block, blocks_per_cu = the emit kernel's grid. Does not synchronise."""
+    return _icmp_err_dev(4, buf, offsets, req, arg, src, ttl, ident0, max_out, out, work, stream, tune)
+
+
+def icmp_err_ipv6_dev(buf, offsets, req, src, arg=None, ttl: int = 64, ident0: int = 0, max_out: int | None = None,
+                      out=None, work=None, stream=None, tune=None) -> dict:
+    """The same for IPv6 (16 address bytes, ICMPv6 types 1-4, quotes of up to 1232 bytes; ident0 is unused)."""
+    return _icmp_err_dev(6, buf, offsets, req, arg, src, ttl, ident0, max_out, out, work, stream, tune)
+
+
+def icmp_req_frag_dev(status, mtu, req, arg, stream=None):
+    """nsx_icmp_req_frag_dev: where status[i] == FRAG_DF (frag_ipv4_dev's status), req[i] = 3 | 4 << 8 and arg[i] =
+    mtu[i] & 0xFFFF; every other entry of req / arg (int32, n each) stays as it was. Returns (req, arg)."""
+    what = "icmp_req_frag_dev"
+    if status is None or mtu is None or req is None or arg is None:
+        raise ValueError(f"{what}: status, mtu, req and arg are required")
+    _span(req, 0, f"{what} req", elem=4)
+    n = req.numel()
+    _span(status, n, f"{what} status", elem=1)
+    _span(mtu, 4 * n, f"{what} mtu", elem=4)
+    _span(arg, 4 * n, f"{what} arg", elem=4)
+    _check(lib().nsx_icmp_req_frag_dev(_dev_ptr(status), _dev_ptr(mtu), n, _dev_ptr(req), _dev_ptr(arg),
+                                       _stream(stream)), f"nsx_{what}")
+    return req, arg
+
+
+def _icmp_req_ttl_dev(ipver: int, buf, offsets, valid, ttl_dec: int, req, arg, stream):
+    what = f"icmp_req_ttl_ipv{ipver}_dev"
+    n = _count(offsets, f"{what} offsets")
+    _span(buf, 0, f"{what} buf", elem=1)
+    if valid is None or req is None or arg is None:
+        raise ValueError(f"{what}: `valid`, `req` and `arg` are required")
+    _span(valid, 8 * ((n + 63) // 64), f"{what} valid", elem=8)
+    _span(req, 4 * n, f"{what} req", elem=4)
+    _span(arg, 4 * n, f"{what} arg", elem=4)
+    if not 0 <= ttl_dec < 1 << 32:  # what a uint32_t can carry; the C call refuses 256 and up (NSX_EINVAL)
+        raise ValueError(f"{what}: ttl_dec must be 0..255, got {ttl_dec}")
+    fn = getattr(lib(), f"nsx_{what}")
+    _check(fn(_dev_ptr(buf), _dev_ptr(offsets), n, _dev_ptr(valid), ttl_dec, _dev_ptr(req), _dev_ptr(arg),
+              _stream(stream)), f"nsx_{what}")
+    return req, arg
+
+
+def icmp_req_ttl_ipv4_dev(buf, offsets, valid, ttl_dec: int, req, arg, stream=None):
+    """nsx_icmp_req_ttl_ipv4_dev: where frame i's valid bit is set, it holds a whole IPv4 header and its TTL is <=
+    ttl_dec (the frames the NAT rewrite refuses on TTL), req[i] = 11 and arg[i] = 0. Returns (req, arg)."""
+    return _icmp_req_ttl_dev(4, buf, offsets, valid, ttl_dec, req, arg, stream)
+
+
+def icmp_req_ttl_ipv6_dev(buf, offsets, valid, ttl_dec: int, req, arg, stream=None):
+    """The same for IPv6: the hop limit, req[i] = 3."""
+    return _icmp_req_ttl_dev(6, buf, offsets, valid, ttl_dec, req, arg, stream)
+
+
+def _icmp_rx_verify_dev(ipver: int, buf, offsets, mask, ip_raw, icmp_raw, type, stream, tune):
+    import torch
+    what = f"icmp_rx_ipv{ipver}_verify_dev"
+    n = _count(offsets, f"{what} offsets")
+    if mask is None:  # never a zero-size tensor, whose address is NULL
+        mask = torch.empty(max((n + 63) // 64, 1), dtype=torch.int64, device=offsets.device)  # u64 bits
+    _span(buf, 0, f"{what} buf")
+    _span(mask, 8 * ((n + 63) // 64), f"{what} mask", elem=8)
+    _span(ip_raw, 2 * n, f"{what} ip_raw", elem=2)
+    _span(icmp_raw, 2 * n, f"{what} icmp_raw", elem=2)
+    _span(type, 2 * n, f"{what} type", elem=2)
+    fn = getattr(lib(), f"nsx_{what}_tuned")
+    raws = (_dev_ptr(ip_raw), _dev_ptr(icmp_raw)) if ipver == 4 else (_dev_ptr(icmp_raw),)
+    _check(fn(_dev_ptr(buf), _dev_ptr(offsets), n, _dev_ptr(mask), *raws, _dev_ptr(type), _stream(stream),
+              _tune(tune)), f"nsx_{what}")
+    return mask
+
+
+def icmp_rx_ipv4_verify_dev(buf, offsets, mask=None, ip_raw=None, icmp_raw=None, type=None, stream=None, tune=None):
+    """ICMP receive verify over packed IPv4 frames: validity bitmask (+ optional raw sums, and type << 8 | code per
+    frame — 0xFFFF unless the bit is set — in `type`, int16)."""
+    return _icmp_rx_verify_dev(4, buf, offsets, mask, ip_raw, icmp_raw, type, stream, tune)
+
+
+def icmp_rx_ipv6_verify_dev(buf, offsets, mask=None, icmp_raw=None, type=None, stream=None, tune=None):
+    """ICMPv6 receive verify over packed IPv6 packets: validity bitmask (+ optional raw sum and type << 8 | code)."""
+    return _icmp_rx_verify_dev(6, buf, offsets, mask, None, icmp_raw, type, stream, tune)
+
+
+def _icmp_echo_reply_dev(ipver: int, buf, offsets, valid, ttl: int, hit, stream):
+    import torch
+    what = f"icmp_echo_reply_ipv{ipver}_dev"
+    n = _count(offsets, f"{what} offsets")
+    words = (n + 63) // 64
+    _span(buf, 0, f"{what} buf", elem=1)
+    if valid is None:
+        raise ValueError(f"{what}: the verify's mask `valid` is required")
+    _span(valid, 8 * words, f"{what} valid", elem=8)
+    if hit is None:  # never a zero-size tensor, whose address is NULL
+        hit = torch.empty(max(words, 1), dtype=torch.int64, device=offsets.device)  # u64 bits
+    _span(hit, 8 * words, f"{what} hit", elem=8)
+    if not 0 <= ttl < 1 << 32:  # what a uint32_t can carry; the C call refuses 256 and up (NSX_EINVAL)
+        raise ValueError(f"{what}: ttl must be 0..255, got {ttl}")
+    fn = getattr(lib(), f"nsx_{what}")
+    _check(fn(_dev_ptr(buf), _dev_ptr(offsets), n, _dev_ptr(valid), ttl, _dev_ptr(hit), _stream(stream)),
+           f"nsx_{what}")
+    return hit
+
+
+def icmp_echo_reply_ipv4_dev(buf, offsets, valid, ttl: int = 64, hit=None, stream=None):
+    """In-place echo reply over packed IPv4 frames (nsx_icmp_echo_reply_ipv4_dev): valid = icmp_rx_ipv4_verify_dev's
+    mask. Echo requests to a unicast address become their replies in `buf` itself: addresses swapped, TTL = ttl, type
+    0, both checksums updated incrementally. Returns `hit`: bit i%64 of hit[i//64] iff frame i was answered (int64
+    words, allocated unless given). Does not synchronise."""
+    return _icmp_echo_reply_dev(4, buf, offsets, valid, ttl, hit, stream)
+
+
+def icmp_echo_reply_ipv6_dev(buf, offsets, valid, ttl: int = 64, hit=None, stream=None):
+    """The same for IPv6 (type 128 becomes 129; the hop limit is covered by no checksum)."""
+    return _icmp_echo_reply_dev(6, buf, offsets, valid, ttl, hit, stream)
 
 
 def fill_splitmix64_dev(buf, seed: int, byte_off: int = 0, stream=None):
